@@ -2,7 +2,14 @@
 """Throughput benchmark of the fused two-tower training step on MI355X.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2|c4|c5|tiny]
-                    [--negatives sampled|in-batch] [--neg N]
+                    [--negatives sampled|in-batch] [--neg N] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the JSON line (the per-kernel entries
+come from event pairs recorded inside the timed steps).  --full adds the measurements that take
+runs of their own: the exact_table_math sub-line, the --kernel-events roofline detail pass, the
+--config c4 bulk gather and the CPU baseline.  --dump-outputs DIR writes what the last timed step
+left with its caller (losses, parameters; large tables as a fixed seeded sample of rows) as
+DIR/<name>.npy, the same inputs on every run with the same arguments.
 
 --gpus N > 1 without WORLD_SIZE in the environment starts the N ranks itself (a child
 `torch.distributed.run --nproc-per-node N`, rendezvous on 127.0.0.1) and prints rank 0's line;
@@ -32,7 +39,7 @@ the row-sharded step of ttamm/sharded.py on a C2 batch of its own users: item re
 (t | a) / (dT | dA) rows go through all-to-alls, the MLP / gate gradients through one
 all-reduce.
 
-The JSON line also carries
+The JSON line also carries (cpu_baseline only with --full)
   kernels:      the step's largest kernels, each timed live with HIP events on the stream it
                 runs on, over the timed steps: the deferred table AdamW replay (rolling slice +
                 both towers' catch-up, + the closing flush's share; VALU-bound), the first
@@ -385,6 +392,43 @@ def gather_bulk(device, rows: int = 50_000_000, dim: int = 128, n: int = 2_000_0
                     "(profiles/pmc_traffic.json c4_gather_bulk, profiles/r06_gather_bulk_*)"}
 
 
+DUMP_ROWS = 4096  # --dump-outputs: rows written per id list of a table with more than 2 x this many rows
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(path: Path, w: "Workload", last_batch, local_ids: bool, seed: int) -> None:
+    """--dump-outputs: what the last timed step and the closing flush left with their caller, as
+    float32 / float64 .npy files: the last step's losses and batch, and every parameter of the
+    model.  A table of more than 2 x DUMP_ROWS rows is written as two row samples: DUMP_ROWS ids
+    drawn uniformly with a fixed seed, and (local_ids: one process, the batch's ids index the
+    tables) the rows of the last batch's first DUMP_ROWS users / positives, which that step
+    updated.  Every row is current here (the flush)."""
+    import numpy as np
+
+    path.mkdir(parents=True, exist_ok=True)
+    eng, c = w.engine, w.c
+    arrays = {"losses": np.asarray(list(eng.last_losses().values()), dtype=np.float64)}
+    users, items = last_batch
+    arrays["batch_users"] = users.cpu().numpy().astype(np.float64)
+    arrays["batch_items"] = items.cpu().numpy().astype(np.float64)
+    by_rows = {c["U"]: users[:DUMP_ROWS], c["I"]: items[:DUMP_ROWS]} if local_ids else {}
+    gen = torch.Generator().manual_seed(seed)
+    for name, p in w.model.named_parameters():
+        t = p.detach()
+        if t.dim() != 2 or t.shape[0] <= 2 * DUMP_ROWS:
+            arrays[name] = t.float().cpu().numpy()
+            continue
+        ids = torch.randint(0, t.shape[0], (DUMP_ROWS,), generator=gen).to(t.device)
+        arrays[name + ".rows_sampled"] = t.index_select(0, ids).float().cpu().numpy()
+        if t.shape[0] in by_rows:
+            arrays[name + ".rows_last_batch"] = t.index_select(0, by_rows[t.shape[0]]).float().cpu().numpy()
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise RuntimeError(f"--dump-outputs: {total} bytes exceed the {DUMP_LIMIT_BYTES}-byte limit")
+    for name, a in arrays.items():
+        np.save(path / f"{name}.npy", a)
+
+
 def cpu_model() -> str:
     try:
         for line in Path("/proc/cpuinfo").read_text().splitlines():
@@ -461,9 +505,16 @@ def main() -> None:
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--config", default="c2", choices=sorted(CONFIGS))
     ap.add_argument("--seed", type=int, default=1234)
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need, each a run of its own after the timed "
+                         "region: the exact_table_math sub-line, the --kernel-events roofline detail pass, the "
+                         "--config c4 bulk gather, the CPU baseline (the --no-* options below drop single ones)")
+    ap.add_argument("--dump-outputs", type=Path, default=None, metavar="DIR",
+                    help="after the timed steps write what the last of them left with its caller (losses, "
+                         "parameters; large tables as a fixed seeded sample of rows) as DIR/<name>.npy")
     ap.add_argument("--cpu-steps", type=int, default=20)
     ap.add_argument("--cpu-warmup", type=int, default=3)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
     ap.add_argument("--dist-backend", default="nccl", choices=["nccl", "gloo"],
                     help="gloo stages the exchanges through host memory (several ranks on one GPU, tests only)")
     ap.add_argument("--eager-adamw", action="store_true",
@@ -496,7 +547,7 @@ def main() -> None:
                     help="every-step: every pair in the timed steps.  roofline: the timed steps carry the "
                          "aux-stream replay pairs, the in-batch and c4 gather pairs only; the main-stream GEMM "
                          "pairs (first layer, wide weight gradient) are timed in a detail pass of K more steps "
-                         "after it (C2 +0.6 %%, within noise: profiles/r06_s29_*).  none: no pairs (the "
+                         "after it, with --full (C2 +0.6 %%, within noise: profiles/r06_s29_*).  none: no pairs (the "
                          "roofline entries then have no live launch durations; the events' own cost)")
     ap.add_argument("--event-kind", choices=["device", "torch"], default="device",
                     help="device: timing events with a device-scope release (HipTimingEvent); torch: "
@@ -555,10 +606,11 @@ def main() -> None:
 
     look_ahead = isinstance(eng, ShardedTrainStep) and not args.no_look_ahead
     nxt = w.batch()
+    last_batch = nxt
 
     def step(**kw) -> None:
-        nonlocal nxt
-        u, p = nxt
+        nonlocal nxt, last_batch
+        u, p = last_batch = nxt
         nxt = w.batch()
         if look_ahead:
             eng.step(u, p, next_batch=nxt, **kw)
@@ -621,8 +673,12 @@ def main() -> None:
         t = torch.tensor([elapsed], device=device if args.dist_backend == "nccl" else "cpu", dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if args.dump_outputs is not None and rank == 0:
+        # here, before any further step: the state is the timed steps' (every table row current)
+        dump_outputs(args.dump_outputs, w, last_batch, local_ids=world == 1 and not emulate and not args.sharded_single,
+                     seed=args.seed)
     exact_line = None
-    if args.exact_line and not args.eager_adamw and not args.exact_table_math and hasattr(eng, "args"):
+    if args.full and args.exact_line and not args.eager_adamw and not args.exact_table_math and hasattr(eng, "args"):
         # the drop-in default's table arithmetic (ttamm.FusedTrainStep(table_adamw_math="exact"),
         # IEEE sqrt / division, bit-identical to torch's AdamW): the same step, K more steps + the
         # flush, timed the same way.  Every row is current here (the flush above), so the switch
@@ -652,7 +708,8 @@ def main() -> None:
                               "sqrt and division in the g = 0 table AdamW, bit-identical to torch): the same "
                               "workload, K steps + the closing flush, right after the main timed region"}
     evs_detail = evs
-    if args.kernel_events == "roofline":
+    detail_pass = args.full and args.kernel_events == "roofline"
+    if detail_pass:
         # detail pass: K more steps (+ the flush) carrying the main-stream GEMM pairs [2, 3] (first
         # feature layer) and [6, 7] (wide weight gradient), for the kernels entries beside the roofline
         evs_detail = [[new_event() for _ in range(NEV)] for _ in range(args.steps)]
@@ -670,6 +727,8 @@ def main() -> None:
 
     def pair_ms(i: int) -> float:  # mean over the timed steps of event pair (i, i + 1); 0 if unused
         tot = 0.0
+        if i in (2, 6) and args.kernel_events == "roofline" and not detail_pass:
+            return 0.0  # the main-stream GEMM pairs are the detail pass's (--full)
         for q in (evs_detail if i in (2, 6) else evs):
             try:
                 tot += q[i].elapsed_time(q[i + 1])
@@ -740,7 +799,7 @@ def main() -> None:
             "wide weight-gradient GEMM launch (dW = dY^T X, split-K slabs; "
             + ", ".join(f"{M}x{Nn}" for _, M, Nn in wide[: len(wide) // 2]) + f" per tower), {impl}",
             sum(2.0 * R * M * Nn for R, M, Nn in wide), pair_ms(6), split_ceiling, "wgrad_wide_bytes_per_launch"))
-    if args.kernel_events == "roofline":
+    if detail_pass:
         for e in kernels:
             e["events"] = "detail pass: K steps after the timed region, the same step with these pairs recorded"
     if in_batch:
@@ -869,7 +928,7 @@ def main() -> None:
         out["exact_table_math"] = exact_line
     if gather is not None:
         out["gather"] = gather
-    if args.config == "c4" and not emulate and world == 1 and args.gather_bulk:
+    if args.full and args.config == "c4" and not emulate and world == 1 and args.gather_bulk:
         out["gather"] = dict(gather or {}, bulk=gather_bulk(device))
     if emulate:
         out["emulated_world"] = shard_world
@@ -877,7 +936,7 @@ def main() -> None:
                                         "(ttamm.sharded.MirrorComm, no interconnect traffic)")
         out["note"] = ("value = this rank's own interactions/s; a W-rank job's aggregate is at most W x value "
                        "(collectives over xGMI not included)")
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and not emulate:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and not emulate:
         try:
             out["cpu_baseline"] = cpu_baseline(c, args.cpu_steps, args.cpu_warmup, args.seed, in_batch=in_batch)
         except Exception as exc:  # reported, not fatal to the GPU measurement

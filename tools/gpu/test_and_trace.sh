@@ -1,8 +1,10 @@
 set -e
 cd $GRAFT_REPO_ROOT
+O=${OUT:-bench_out}  # output directory
+mkdir -p $O
 export TMPDIR=/tmp
-timeout -k 10 600 python -u -m pytest tests -m gpu -x -q --timeout 300 --timeout-method thread > gpurun_out/t3.log 2>&1
-timeout -k 10 300 python bench.py --no-cpu-baseline > gpurun_out/b3_c2.json 2> gpurun_out/b3_c2.err
-timeout -k 10 300 rocprofv3 --kernel-trace --output-format csv -d gpurun_out/trace_c2 -o run -- python3 bench.py --no-cpu-baseline --steps 10 --warmup 3 $BENCH_ARGS > gpurun_out/trace_c2_bench.json 2> gpurun_out/trace_c2.err
-find gpurun_out/trace_c2 -name "*kernel_trace.csv" -exec cp {} gpurun_out/trace_c2_kernels.csv \;
-rm -rf gpurun_out/trace_c2
+timeout -k 10 600 python -u -m pytest tests -m gpu -x -q --timeout 300 --timeout-method thread > $O/t3.log 2>&1
+timeout -k 10 300 python bench.py --full --no-cpu-baseline > $O/b3_c2.json 2> $O/b3_c2.err
+timeout -k 10 300 rocprofv3 --kernel-trace --output-format csv -d $O/trace_c2 -o run -- python3 bench.py --full --no-cpu-baseline --steps 10 --warmup 3 $BENCH_ARGS > $O/trace_c2_bench.json 2> $O/trace_c2.err
+find $O/trace_c2 -name "*kernel_trace.csv" -exec cp {} $O/trace_c2_kernels.csv \;
+rm -rf $O/trace_c2
