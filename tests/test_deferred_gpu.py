@@ -22,7 +22,7 @@ ROOT = Path(__file__).resolve().parents[1]
 
 
 def _engine(prob, *, deferred: bool, slices: int, sparse: bool = True, overlap: bool = True, math: str = "fast",
-            aux_cus=None, sgd: dict | None = None):
+            aux_cus=None, sgd: dict | None = None, gradient_clip_norm: float | None = None):
     from gpu_helpers import ttamm_model_from
 
     model = ttamm_model_from(prob)
@@ -39,7 +39,7 @@ def _engine(prob, *, deferred: bool, slices: int, sparse: bool = True, overlap: 
                                user_features=prob.user_features.cuda(), item_features=prob.item_features.cuda(),
                                loss_weights=LOSS_WEIGHTS, max_batch=prob.shape.B, seed=11,
                                deferred_adamw=deferred, replay_slices=slices, overlap=overlap,
-                               table_adamw_math=math, aux_cus=aux_cus)
+                               table_adamw_math=math, aux_cus=aux_cus, gradient_clip_norm=gradient_clip_norm)
     return model, opts, eng
 
 
@@ -53,20 +53,25 @@ def _state(model, opts):
     return out
 
 
-def _run(prob, steps, *, deferred, slices, sparse=True, flush_at=None, lr_change_at=None, overlap=True, math="fast",
-         aux_cus=None, sgd=None):
-    model, opts, eng = _engine(prob, deferred=deferred, slices=slices, sparse=sparse, overlap=overlap, math=math,
-                               aux_cus=aux_cus, sgd=sgd)
+def _batches(prob, steps):
     gen = torch.Generator().manual_seed(3)
+    for _ in range(steps):
+        users = torch.randint(0, prob.shape.U, (prob.shape.B,), generator=gen)
+        pos = torch.tensor([sorted(prob.positives[int(u)])[0] for u in users], dtype=torch.long)
+        yield users.cuda(), pos.cuda()
+
+
+def _run(prob, steps, *, deferred, slices, sparse=True, flush_at=None, lr_change_at=None, overlap=True, math="fast",
+         aux_cus=None, sgd=None, gradient_clip_norm=None):
+    model, opts, eng = _engine(prob, deferred=deferred, slices=slices, sparse=sparse, overlap=overlap, math=math,
+                               aux_cus=aux_cus, sgd=sgd, gradient_clip_norm=gradient_clip_norm)
     losses = []
-    for k in range(steps):
+    for k, (users, pos) in enumerate(_batches(prob, steps)):
         if lr_change_at is not None and k == lr_change_at:
             for o in opts:
                 for g in o.param_groups:
                     g["lr"] = 3e-3
-        users = torch.randint(0, prob.shape.U, (prob.shape.B,), generator=gen)
-        pos = torch.tensor([sorted(prob.positives[int(u)])[0] for u in users], dtype=torch.long)
-        eng.step(users.cuda(), pos.cuda())
+        eng.step(users, pos)
         losses.append(eng.last_losses()["total"])
         if flush_at is not None and k == flush_at:
             eng.flush()
@@ -119,6 +124,63 @@ def test_aux_stream_overlap_bitwise(deferred, sparse):
     for k in one:
         assert torch.equal(one[k], two[k]), k
         assert torch.equal(one[k], three[k]), k
+
+
+_EAGER_DENSE_ID: dict = {}
+
+
+def _eager_dense_id(clip):
+    """The eager one-stream run of the flush tests' problem (dense ID tables), once per clip norm."""
+    if clip not in _EAGER_DENSE_ID:
+        prob = make_problem(Shape(), seed=5)
+        _EAGER_DENSE_ID[clip], _ = _run(prob, 9, deferred=False, slices=3, sparse=False, overlap=False,
+                                        gradient_clip_norm=clip)
+    return _EAGER_DENSE_ID[clip]
+
+
+@pytest.mark.parametrize("clip,aux_cus", [(1.0, None), (None, None), (1.0, 16)],
+                         ids=["clip", "dense-id", "clip-aux-cus"])
+def test_flush_without_sync_is_ordered(clip, aux_cus):
+    """flush() right behind the last step, no host sync in between: the flush's replay (on the aux
+    stream when there is one) must follow that step's table updates on the caller's stream, and
+    the caller's stream the replay.  The cases are the ones whose row updates run on the caller's
+    stream although an aux stream exists: gradient clipping (the updates wait for the global norm)
+    and deferred dense ID tables (no fork); with aux_cus the flush itself runs on the caller's
+    stream.  Clipping needs dense ID tables (FusedTrainStep raises NotImplementedError for sparse
+    ones, as torch's clip_grad_norm_ does), so every case has them.  The snapshot is taken on the
+    current stream right after the flush (the clones are stream-ordered behind it), before any
+    synchronisation; it equals the eager one-stream run bit for bit.  (The optimizers' `step`
+    counters are written by finish() and are not part of the snapshot.)"""
+    prob = make_problem(Shape(), seed=5)
+    model, opts, eng = _engine(prob, deferred=True, slices=3, sparse=False, overlap=True, aux_cus=aux_cus,
+                               gradient_clip_norm=clip)
+    for users, pos in _batches(prob, 9):
+        eng.step(users, pos)
+    eng.flush()
+    snap = _state(model, opts)
+    eng.finish()
+    eager = _eager_dense_id(clip)
+    assert snap.keys() == eager.keys()
+    for k in eager:
+        if not k.endswith(".step"):
+            assert torch.equal(snap[k], eager[k]), k
+
+
+@pytest.mark.parametrize("deferred", [False, True], ids=["eager", "deferred"])
+def test_steps_applied_visible_after_stream_sync(deferred):
+    """Gradient clipping with an aux stream: after a synchronise of the caller's stream alone every
+    enqueued step is counted in steps_applied (INTEGRATION.md "Streams"; _status_error reads it
+    there).  Eager is the case in which the count used to be published on the aux stream although
+    clipping keeps the step's closing join away; deferred dense ID tables run on one stream."""
+    prob = make_problem(Shape(), seed=5)
+    model, opts, eng = _engine(prob, deferred=deferred, slices=3, sparse=False, overlap=True, gradient_clip_norm=1.0)
+    for users, pos in _batches(prob, 5):
+        eng.step(users, pos)
+    torch.cuda.current_stream().synchronize()
+    applied, status = int(eng.steps_applied.item()), int(eng.status.item())
+    eng.finish()
+    assert applied == 5
+    assert status == 0
 
 
 def test_deferred_c2_equals_eager():

@@ -86,9 +86,6 @@ struct TowerWs {
     uint16_t* w16 = nullptr;  // bf16 towers with bf16 feature rows: the weight rounded, padded to % 8
     uint16_t* gw16 = nullptr;  // bf16 gated towers (D == Hg in {128, 256}): the fused gate's weight images
     bool gw16_ready = false;   // formed by this call's forward (the weights do not change before its backward)
-    // wpad / w16 formed by this step's prologue launch (ttamm_train_step; the standalone tower
-    // entry points form them themselves)
-    bool weight_prepped = false;
     int wgrad_rps[kWgradClasses] = {512, 512, 512, 512};  // split-K rows of the weight gradients, per tile class
 };
 
@@ -161,6 +158,9 @@ int validate_tower(const ttamm_tower& T, const char* name, int D, bool training)
     if (T.fusion != TTAMM_FUSION_IDENTITY) {
         TTAMM_REQUIRE(T.features != nullptr && T.feat_dim > 0, n + ": fusion needs feature rows");
         TTAMM_REQUIRE(T.feat_ld >= T.feat_dim, n + ": feature row stride too small");
+        // the feature rows are [id.rows, feat_ld]: the weight gradient keeps their gathered row ids as int32
+        TTAMM_REQUIRE(T.id.rows < (int64_t(1) << 31), n + ": feature rows of 2^31 rows or more are not supported "
+                                                          "(the weight gradient gathers them by int32 row ids)");
         TTAMM_REQUIRE(T.feat_ld % 4 == 0 && (uintptr_t)T.features % 16 == 0,
                       n + ": feature rows must be 16-byte aligned (row stride % 4 == 0)");
         if (T.features_bf16)
@@ -274,6 +274,17 @@ void plan_scratch(Arena& ar, const ttamm_step_args& A, StepWs& ws) {
     ws.prologue_done = ar.take<uint32_t>(1);
 }
 
+// the split-K slabs of a tower's weight gradients (w.wgrad_rps chosen before): the feature
+// encoder's layers, then the fusion's
+void plan_slabs(Arena& ar, const ttamm_tower& T, int64_t R, TowerWs& w) {
+    if (T.fusion == TTAMM_FUSION_IDENTITY) return;
+    for (int i = 0; i < T.n_linear + fusion_linears(T); ++i) {
+        const ttamm_linear& L = i < T.n_linear ? T.linear[i] : T.gate[i - T.n_linear];
+        w.slab[i < T.n_linear ? i : TTAMM_MAX_LINEAR + i - T.n_linear] = ar.take<float>(
+            wgrad_slab_floats((int)R, L.out_features, L.in_features, w.wgrad_rps[wgrad_class(L.out_features)]));
+    }
+}
+
 void plan_coalesce(Arena& ar, CoalesceWs& co, int64_t R) {
     co.keys_out = ar.take<int32_t>(R);
     co.vals_out = ar.take<int32_t>(R);
@@ -342,21 +353,7 @@ int plan(Arena& ar, const ttamm_step_args& A, StepWs& ws) {
             w.dA_ld = D;
             w.dA_split = dA_rows;
         }
-        if (T.fusion != TTAMM_FUSION_IDENTITY) {
-            for (int l = 0; l < T.n_linear; ++l) {
-                const ttamm_linear& L = T.linear[l];
-                w.slab[l] = ar.take<float>(
-                    wgrad_slab_floats((int)R, L.out_features, L.in_features, w.wgrad_rps[wgrad_class(L.out_features)]));
-            }
-        }
-        {
-            for (int q = 0; q < fusion_linears(T); ++q) {
-                const ttamm_linear& L = T.gate[q];
-                w.slab[TTAMM_MAX_LINEAR + q] =
-                    ar.take<float>(wgrad_slab_floats((int)R, L.out_features, L.in_features,
-                                                     w.wgrad_rps[wgrad_class(L.out_features)]));
-            }
-        }
+        plan_slabs(ar, T, R, w);
         plan_coalesce(ar, w.co, R);
         if (A.adam_history && A.history_capacity > 1) {
             const int cap = A.history_capacity;
@@ -491,24 +488,26 @@ bool generic_gate_forced() {
     return v && v[0] == '1';
 }
 
-bool gate_group(const ttamm_tower* const* T, TowerWs* const* W, int ntowers, int D, bool mimic, GateArgs& ga) {
-    std::memset(&ga, 0, sizeof(ga));
+// Whether the gated towers of a grouped launch all run on one fused gate kernel, and which: their
+// common hidden width and form (planes 0: gate.hip, 1 / 3: gate16.hip).  has16[k]: tower k has
+// gate16 weight images (plan() gives a gated tower some exactly when gate16_supported).
+bool gate_choice(const ttamm_tower* const* T, const bool* has16, int ntowers, int D, int& hg, int& planes) {
+    hg = planes = -1;
     if (generic_gate_forced()) return false;
     // TTAMM_GATE16_SPLIT=1: fp32 towers at D = 96 on gate16.hip's split-bf16 form instead of gate.hip
     // (fp32 MFMA).  Measured slower at C2 (forward 71 vs 61 us, backward 72 vs 70, step 0.695 vs
     // 0.655 ms, profiles/r05_s20_gate16_split.txt): the kernels are latency-bound, not MFMA-bound
     const char* e16 = dev_env("TTAMM_GATE16_SPLIT");
     const bool split16 = e16 && e16[0] == '1';
-    int hg = -1, planes = -1;
     for (int k = 0; k < ntowers; ++k) {
         const ttamm_tower& t = *T[k];
         if (t.fusion != TTAMM_FUSION_GATED) continue;
         const int h = t.gate[0].out_features;
         int np;
         if (t.matmul_bf16) {
-            if (!(gate16_supported(D, h, 1) && W[k]->gw16)) return false;
+            if (!(gate16_supported(D, h, 1) && has16[k])) return false;
             np = 1;
-        } else if (split16 && gate16_supported(D, h, 3) && W[k]->gw16) {
+        } else if (split16 && gate16_supported(D, h, 3) && has16[k]) {
             np = 3;
         } else if (gate_fused_supported(D, h)) {
             np = 0;
@@ -519,7 +518,15 @@ bool gate_group(const ttamm_tower* const* T, TowerWs* const* W, int ntowers, int
         hg = h;
         planes = np;
     }
-    if (hg < 0) return false;
+    return hg >= 0;
+}
+
+bool gate_group(const ttamm_tower* const* T, TowerWs* const* W, int ntowers, int D, bool mimic, GateArgs& ga) {
+    std::memset(&ga, 0, sizeof(ga));
+    bool has16[2] = {};
+    for (int k = 0; k < ntowers; ++k) has16[k] = W[k]->gw16 != nullptr;
+    int hg, planes;
+    if (!gate_choice(T, has16, ntowers, D, hg, planes)) return false;
     ga.planes = planes;
     ga.images_ready = 1;
     for (int k = 0; k < ntowers; ++k) {
@@ -574,6 +581,7 @@ bool gate_out_epilogue() {
     return on;
 }
 enum { FWD_GATHER = 1, FWD_FUSION = 2, FWD_FEAT = 4, FWD_MLP = FWD_GATHER | FWD_FEAT, FWD_ALL = 7 };
+int forward_fusion(const ttamm_tower* T[2], TowerWs* W[2], int D, bool mimic, hipStream_t s, int ntowers);
 int tower_forward(const ttamm_tower* T[2], TowerWs* W[2], const ttamm_batch& bt, int D, bool mimic, hipStream_t s,
                   int ntowers, void* const* l0_events = nullptr, int part = FWD_ALL, hipEvent_t after_l0 = nullptr) {
     int rc;
@@ -646,17 +654,15 @@ int tower_forward(const ttamm_tower* T[2], TowerWs* W[2], const ttamm_batch& bt,
                 p.ldb = L.in_features;
                 if (l == 0 && w.w16) {  // bf16 operands in memory (C5 layer 1)
                     const int kp = round8(L.in_features);
-                    if (!w.weight_prepped &&
-                        (rc = launch_to_bf16(L.weight, L.out_features, L.in_features, L.in_features, w.w16, kp, s)))
+                    if ((rc = launch_to_bf16(L.weight, L.out_features, L.in_features, L.in_features, w.w16, kp, s)))
                         return rc;
                     p.A16 = t.features_bf16;
                     p.lda = t.feat_bf16_ld;
                     p.B16 = w.w16;
                     p.ldb = kp;
                 } else if (l == 0 && w.wpad) {
-                    if (!w.weight_prepped)
-                        pads.seg[pads.count++] = PadSeg{L.weight, L.out_features, L.in_features, L.in_features, w.wpad,
-                                                        round4(L.in_features)};
+                    pads.seg[pads.count++] = PadSeg{L.weight, L.out_features, L.in_features, L.in_features, w.wpad,
+                                                    round4(L.in_features)};
                     p.B = w.wpad;
                     p.ldb = round4(L.in_features);
                 }
@@ -708,8 +714,12 @@ int tower_forward(const ttamm_tower* T[2], TowerWs* W[2], const ttamm_batch& bt,
             if (l == 0 && after_l0) TTAMM_HIP(hipEventRecord(after_l0, s));
         }
     }
-    if (!(part & FWD_FUSION)) return TTAMM_OK;
-    // fusion
+    return part & FWD_FUSION ? forward_fusion(T, W, D, mimic, s, ntowers) : TTAMM_OK;
+}
+
+// part FWD_FUSION: the gate (fused kernel or two GEMMs + mix), the concat projection, or the combine
+int forward_fusion(const ttamm_tower* T[2], TowerWs* W[2], int D, bool mimic, hipStream_t s, int ntowers) {
+    int rc;
     GateArgs ga;
     const bool fused_gate = gate_group(T, W, ntowers, D, mimic, ga);
     if ((rc = require_fused_for_units(T, W, ntowers, fused_gate))) return rc;
@@ -825,6 +835,7 @@ bool wgrad_x16() {
 // part BWD_GATE: the fusion's backward (dEF, the ID rows' gradient with it); BWD_MLP: the feature
 // MLP's dgrad chain and every weight gradient
 enum { BWD_GATE = 1, BWD_MLP = 2, BWD_ALL = 3 };
+int tower_wgrads(const ttamm_tower* T[2], TowerWs* W[2], int D, hipStream_t s, int ntowers, void* const* wg_events);
 int tower_backward(const ttamm_tower* T[2], TowerWs* W[2], int D, hipStream_t s, int ntowers,
                    void* const* wg_events = nullptr, int part = BWD_ALL) {
     int rc;
@@ -945,75 +956,50 @@ int tower_backward(const ttamm_tower* T[2], TowerWs* W[2], int D, hipStream_t s,
         }
         if ((rc = bb.run(s))) return rc;
     }
-    // all weight gradients in one grouped launch
+    return tower_wgrads(T, W, D, s, ntowers, wg_events);
+}
+
+// dW = dY^T X ([M, N]) and db = sum dY over the tower's rows, into the gradient arena through `slab`
+WgradProblem wgrad_problem(const ttamm_tower& t, const TowerWs& w, const float* dY, int64_t ld_dy, const float* X,
+                           int64_t ld_x, int M, int N, float* grad_w, float* grad_b, float* slab) {
+    WgradProblem p{};
+    p.bf16 = t.matmul_bf16;
+    p.dY = dY, p.ld_dy = ld_dy;
+    p.X = X, p.ld_x = ld_x;
+    p.R = (int)w.R, p.M = M, p.N = N;
+    p.grad_w = grad_w, p.grad_b = grad_b, p.slab = slab;
+    p.rows_per_split = w.wgrad_rps[wgrad_class(M)];
+    return p;
+}
+
+// all weight gradients in one grouped launch
+int tower_wgrads(const ttamm_tower* T[2], TowerWs* W[2], int D, hipStream_t s, int ntowers, void* const* wg_events) {
     WgradBatch wb;
     std::memset(&wb, 0, sizeof(wb));
     for (int k = 0; k < ntowers; ++k) {
         const ttamm_tower& t = *T[k];
         TowerWs& w = *W[k];
         if (t.fusion == TTAMM_FUSION_IDENTITY) continue;
+        float* const* gslab = w.slab + TTAMM_MAX_LINEAR;
         if (t.fusion == TTAMM_FUSION_GATED) {
             const int Hg = t.gate[0].out_features;
-            WgradProblem g2{};
-            g2.bf16 = t.matmul_bf16;
-            g2.dY = w.dq;
-            g2.ld_dy = D;
-            g2.X = w.z;
-            g2.ld_x = Hg;
-            g2.R = (int)w.R;
-            g2.M = D;
-            g2.N = Hg;
-            g2.grad_w = w.ggw[1];
-            g2.grad_b = w.ggb[1];
-            g2.slab = w.slab[TTAMM_MAX_LINEAR + 1];
-            g2.rows_per_split = w.wgrad_rps[wgrad_class(g2.M)];
-            wb.p[wb.count++] = g2;
-            WgradProblem g1{};
-            g1.bf16 = t.matmul_bf16;
-            g1.dY = w.dz;
-            g1.ld_dy = Hg;
-            g1.X = w.ef;
-            g1.ld_x = 2 * D;
-            g1.R = (int)w.R;
-            g1.M = Hg;
-            g1.N = 2 * D;
-            g1.grad_w = w.ggw[0];
-            g1.grad_b = w.ggb[0];
-            g1.slab = w.slab[TTAMM_MAX_LINEAR];
-            g1.rows_per_split = w.wgrad_rps[wgrad_class(g1.M)];
-            wb.p[wb.count++] = g1;
+            wb.p[wb.count++] = wgrad_problem(t, w, w.dq, D, w.z, Hg, D, Hg, w.ggw[1], w.ggb[1], gslab[1]);
+            wb.p[wb.count++] = wgrad_problem(t, w, w.dz, Hg, w.ef, 2 * D, Hg, 2 * D, w.ggw[0], w.ggb[0], gslab[0]);
         }
-        if (t.fusion == TTAMM_FUSION_CONCAT) {  // dP = dT^T [e | f], db = sum dT
-            WgradProblem pp{};
-            pp.bf16 = t.matmul_bf16;
-            pp.dY = w.dT;
-            pp.ld_dy = w.dT_ld;
-            pp.X = w.ef;
-            pp.ld_x = efw(t);
-            pp.R = (int)w.R;
-            pp.M = D;
-            pp.N = efw(t);
-            pp.grad_w = w.ggw[0];
-            pp.grad_b = w.ggb[0];
-            pp.slab = w.slab[TTAMM_MAX_LINEAR];
-            pp.rows_per_split = w.wgrad_rps[wgrad_class(pp.M)];
-            wb.p[wb.count++] = pp;
-        }
+        if (t.fusion == TTAMM_FUSION_CONCAT)  // dP = dT^T [e | f], db = sum dT
+            wb.p[wb.count++] =
+                wgrad_problem(t, w, w.dT, w.dT_ld, w.ef, efw(t), D, efw(t), w.ggw[0], w.ggb[0], gslab[0]);
         for (int l = t.n_linear - 1; l >= 0; --l) {
             const ttamm_linear& L = t.linear[l];
-            WgradProblem p{};
-            p.bf16 = t.matmul_bf16;
-            if (l == t.n_linear - 1) {
-                p.dY = uses_ef(t) ? w.dEF + t.id.dim : w.dT;
-                p.ld_dy = uses_ef(t) ? efw(t) : w.dT_ld;
-            } else {
-                p.dY = w.dhid[l];
-                p.ld_dy = L.out_features;
-            }
+            const bool last = l == t.n_linear - 1;
+            const float* dY = !last ? w.dhid[l] : uses_ef(t) ? w.dEF + t.id.dim : w.dT;
+            const int64_t ld_dy = !last ? L.out_features : uses_ef(t) ? efw(t) : w.dT_ld;
+            WgradProblem p = l == 0 ? wgrad_problem(t, w, dY, ld_dy, t.features, t.feat_ld, L.out_features,
+                                                    L.in_features, w.gw[l], w.gb[l], w.slab[l])
+                                    : wgrad_problem(t, w, dY, ld_dy, w.hid[l - 1], t.linear[l - 1].out_features,
+                                                    L.out_features, L.in_features, w.gw[l], w.gb[l], w.slab[l]);
             if (l == 0) {
-                p.X = t.features;
                 p.x_idx = w.fidx;
-                p.ld_x = t.feat_ld;
                 if (uses_w16(t) && wgrad_x16()) {  // the same bf16 values, from the tower's bf16 copy
                     p.X16 = t.features_bf16;
                     p.ld_x16 = t.feat_bf16_ld;
@@ -1022,22 +1008,11 @@ int tower_backward(const ttamm_tower* T[2], TowerWs* W[2], int D, hipStream_t s,
                     p.X3p = t.features_planes;
                     p.ld_x3 = t.feat_planes_ld;
                 }
-            } else {
-                p.X = w.hid[l - 1];
-                p.ld_x = t.linear[l - 1].out_features;
             }
-            p.R = (int)w.R;
-            p.M = L.out_features;
-            p.N = L.in_features;
-            p.grad_w = w.gw[l];
-            p.grad_b = w.gb[l];
-            p.slab = w.slab[l];
-            p.rows_per_split = w.wgrad_rps[wgrad_class(p.M)];
             wb.p[wb.count++] = p;
         }
     }
-    if ((rc = launch_wgrad(wb, s, wg_events))) return rc;
-    return TTAMM_OK;
+    return launch_wgrad(wb, s, wg_events);
 }
 
 // Deferred exact AdamW(g = 0) (ttamm.h ttamm_table.last_step).
@@ -1051,18 +1026,22 @@ struct Deferred {
     int fast = 0;  // TTAMM_G0_FAST arithmetic for the g = 0 updates
     int sgd = 0;   // torch.optim.SGD dense group: the g = 0 replay is sgd_elem's (replay_sgd_kernel)
     const uint32_t* status = nullptr;  // poisoned: the step writes nothing
-    // one-process step with the aux stream: the rolling slice runs there (replay_slice_aux)
-    // instead of at the end of the main stream's step
-    bool slice_on_aux = false;
-    // TTAMM_SLICE_LATE=1: launched when the main stream reaches the table updates (overlapping
-    // the memory-bound row updates and the next step's prologue) rather than behind the grouping
-    // (overlapping the backward GEMMs).  Measured at C2: the weight-gradient GEMM runs uncontended
-    // (132 -> 76 us) but the row updates slow by as much, step 0.7326 vs 0.7280 ms
-    // (profiles/r03_c2_slice_late_vs_early_s16.txt) — so behind the grouping stays the default.
-    // (Started once the gate backward is enqueued, overlapping dgrad + the weight gradients
-    // instead of the gate backward: 0.745 vs 0.712-0.720 ms, profiles/r03_c2_slice_point_s20.txt.)
-    bool slice_late = false;
 };
+
+// The part of a replay launch that the optimizer fixes; the caller adds the row segments.
+ReplayArgs replay_header(const Deferred& df, int32_t target, int stamp) {
+    ReplayArgs ra;
+    std::memset(&ra, 0, sizeof(ra));
+    ra.hist = df.hist;
+    ra.cap = df.cap;
+    ra.decoupled = df.decoupled;
+    ra.sgd = df.sgd;
+    ra.fast_g0 = df.fast;
+    ra.status = df.status;
+    ra.target = target;
+    ra.stamp = stamp;
+    return ra;
+}
 
 // The tables of a tower that belong to the dense (AdamW) group.
 int dense_tables(const ttamm_tower& t, bool mimic, const ttamm_table* out[2]) {
@@ -1088,16 +1067,7 @@ ReplaySeg replay_seg(const ttamm_table& tb) {
 // table's rows brought to `target` (every row's lag stays below the history ring).
 int replay_slice(const ttamm_tower* const* T, int n, bool mimic, const Deferred& df, int32_t target, int stamp,
                  void* const* events, hipStream_t s) {
-    ReplayArgs ra;
-    std::memset(&ra, 0, sizeof(ra));
-    ra.hist = df.hist;
-    ra.cap = df.cap;
-    ra.decoupled = df.decoupled;
-    ra.sgd = df.sgd;
-    ra.fast_g0 = df.fast;
-    ra.status = df.status;
-    ra.target = target;
-    ra.stamp = stamp;
+    ReplayArgs ra = replay_header(df, target, stamp);
     const int slice = (int)(((int64_t)target % df.slices + df.slices) % df.slices);
     for (int k = 0; k < n; ++k) {
         const ttamm_table* tabs[2];
@@ -1131,16 +1101,7 @@ int tower_prepare_a(const ttamm_tower& t, TowerWs& w, bool mimic, const Deferred
     int32_t* lasts[2] = {tabs[0]->last_step, n > 1 ? tabs[1]->last_step : nullptr};
     if ((rc = launch_catchup_list(w.idx, w.R, w.co.first, lasts, n, df.step - 1, df.cap, w.cl, df.status, s)))
         return rc;
-    ReplayArgs ra;
-    std::memset(&ra, 0, sizeof(ra));
-    ra.hist = df.hist;
-    ra.cap = df.cap;
-    ra.decoupled = df.decoupled;
-    ra.sgd = df.sgd;
-    ra.fast_g0 = df.fast;
-    ra.status = df.status;
-    ra.target = df.step - 1;
-    ra.stamp = 0;  // stamped by the list build
+    ReplayArgs ra = replay_header(df, df.step - 1, 0);  // stamped by the list build
     for (int i = 0; i < n; ++i) {
         ReplaySeg g = replay_seg(*tabs[i]);
         g.row_lo = 0;
@@ -1164,16 +1125,7 @@ int towers_prepare_a(const ttamm_tower* const* T, TowerWs* const* W, int n, bool
     ps.target = df.step - 1;
     ps.cap = df.cap;
     ps.status = df.status;
-    ReplayArgs ra;
-    std::memset(&ra, 0, sizeof(ra));
-    ra.hist = df.hist;
-    ra.cap = df.cap;
-    ra.decoupled = df.decoupled;
-    ra.sgd = df.sgd;
-    ra.fast_g0 = df.fast;
-    ra.status = df.status;
-    ra.target = df.step - 1;
-    ra.stamp = 0;  // stamped by the list build
+    ReplayArgs ra = replay_header(df, df.step - 1, 0);  // stamped by the list build
     for (int k = 0; k < n; ++k) {
         const ttamm_tower& t = *T[k];
         TowerWs& w = *W[k];
@@ -1211,24 +1163,24 @@ int towers_prepare_a(const ttamm_tower* const* T, TowerWs* const* W, int n, bool
     return launch_replay(ra, s, ev);
 }
 
-int tower_prepare_b(const ttamm_tower& t, TowerWs& w, hipStream_t s) {
-    return launch_coalesce_group(w.idx, w.R, t.id.rows, w.co, s);
-}
-
 int tower_prepare(const ttamm_tower& t, TowerWs& w, bool mimic, const Deferred& df, hipStream_t s,
                   void* const* ev = nullptr) {
     int rc;
     if ((rc = tower_prepare_a(t, w, mimic, df, s, ev))) return rc;
-    return tower_prepare_b(t, w, s);
+    return launch_coalesce_group(w.idx, w.R, t.id.rows, w.co, s);  // part B
 }
 
 // Fork / join events of the aux stream, one set per host thread, device and aux stream (reused
 // across steps: a wait binds to the record that precedes it; per aux stream, so the engines of
-// in-process ranks — each with its own aux stream — never wait on one another's records).  [0] fork, [1] rows current (before the
-// fusion), [2] rows grouped (before the table updates), [3] main stream at the table updates
-// (the late slice's start), [4] main stream after the fusion backward (the row updates' start
-// on the aux stream), [5] aux stream after the row updates (joined at the step's end).
-constexpr int kAuxEvents = 6;
+// in-process ranks — each with its own aux stream — never wait on one another's records).
+enum AuxEvent {
+    EV_FORK = 0,  // main: the aux prologue may start
+    EV_CURRENT,   // aux: the batch's rows are current (before the fusion)
+    EV_GROUPED,   // aux: the batch's rows are grouped (before the table updates)
+    EV_TO_AUX,    // main: the tables are the aux stream's (after the fusion backward; at a flush)
+    EV_FROM_AUX,  // aux: its table writes are done (joined at the step's / the flush's end)
+    kAuxEvents
+};
 // Device-scope fork / join: both streams are on this device, so an agent-scope release / acquire
 // (what every kernel boundary already does) orders their memory.  The default system-scope fence
 // of an event record / wait added ≈2 µs of main-stream idle at each of the step's event
@@ -1263,50 +1215,90 @@ int aux_events(hipEvent_t ev[kAuxEvents], hipStream_t aux) {
     return TTAMM_OK;
 }
 
-bool overlapped(const ttamm_tower* const* T, int n, const Deferred& df, hipStream_t s, hipStream_t aux) {
-    bool overlap = aux != nullptr && aux != s;
-    for (int k = 0; k < n; ++k)
-        if (df.on && T[k]->id.optimizer == TTAMM_OPT_DENSE) overlap = false;
-    return overlap;
+// A deferred dense ID table is read by the step's first gather, which must then follow the
+// catch-up of its rows: nothing to run beside, the step stays on one stream.
+bool overlapped(const ttamm_step_args& A, const Deferred& df) {
+    return !(df.on && (A.user.id.optimizer == TTAMM_OPT_DENSE || A.item.id.optimizer == TTAMM_OPT_DENSE));
 }
 
-// tower_prepare of `n` towers, then their forward.  With an aux stream the index-only prologue
-// runs there while `s` gathers ID rows and runs the feature MLP: part A (count + deferred
-// catch-up) first, joined before the fusion, whose epilogue reads the mimic rows; then part B
-// (grouping), joined by table_updates.  A deferred dense ID table is read by the first gather,
-// so that case stays serial.
+// Where the launches of one ABI call (train step, phase call, flush) go — the caller's stream `s`
+// or the aux stream — and what orders the two.  Built once per call by stream_plan.  Invariant:
+//  (a) Whatever a call enqueues on `aux` that writes state the caller may read after syncing `s`
+//      (tables, moments, last_step, steps_applied, the history ring) is joined to `s` before the
+//      call returns: the catch-up by EV_CURRENT, which the fusion waits for; the row updates, the
+//      loss and the step-begin by EV_FROM_AUX, rows_beside_mlp's last operation.
+//  (b) The rolling slice needs no join of its own: the next catch-up or flush runs on `aux` behind
+//      it and supersedes it.  (`slice` implies `rows` — clipping needs dense ID tables, and deferred
+//      ones leave no fork — so (a)'s join happens to cover it.)
+//  (c) A flush orders `aux` behind `s` before its replay, then `s` behind `aux` — unless
+//      `tables_on_aux`: the steps' writers of the tables are on `aux` already.
+// The grouping (EV_GROUPED) writes workspace only; its readers on `s` wait for it (join_grouping),
+// in a later phase call if need be.
+struct StreamPlan {
+    int rc;           // TTAMM_OK, or why the aux events could not be made
+    hipStream_t s;
+    hipStream_t aux;  // null: no usable aux stream, every launch goes to s
+    hipEvent_t ev[kAuxEvents];
+    // index prologue (gather, catch-up, grouping) on aux beside the feature MLP: see overlapped
+    const bool fork;
+    // bf16 towers fork after the first layer's GEMM (its one-block-per-CU tiles otherwise wait for
+    // CUs behind the catch-up replay), and their ID gather stays on s
+    const bool late_fork;
+    // one process, deferred: the previous step's rolling slice on aux, beside the GEMMs (sharded:
+    // it closes the table updates, on their stream)
+    const bool slice;
+    // touched-row updates on aux beside the MLP backward, joined at the call's end (one process: the
+    // loss finalize and the step-begin with them; sharded: TOWERS_BWD with item rows, the other
+    // phases update on s).  Not with clipping: the updates wait for the global norm.
+    const bool rows;
+    // one process with `rows`: every writer of the tables runs on aux (s only reads them, before
+    // EV_TO_AUX), so a flush there follows them without waiting for the tail of s
+    const bool tables_on_aux;
+};
+
+StreamPlan stream_plan(const ttamm_step_args& A, const Deferred& df, bool clip_on, hipStream_t s) {
+    hipStream_t a = static_cast<hipStream_t>(A.aux_stream);
+    hipStream_t aux = (a != nullptr && a != s) ? a : nullptr;
+    const bool fork = aux != nullptr && overlapped(A, df);
+    const bool rows = fork && !clip_on && (!sharded(A) || A.n_item_rows > 0);
+    StreamPlan p{TTAMM_OK, s, aux, {}, fork, fork && A.user.matmul_bf16 != 0, fork && df.on && !sharded(A), rows,
+                 rows && !sharded(A)};
+    if (aux) p.rc = aux_events(p.ev, aux);
+    return p;
+}
+
+// tower_prepare of `n` towers, then their forward.  With pl.fork the index-only prologue runs on
+// the aux stream while `s` runs the feature MLP: part A (count + deferred catch-up) first, joined
+// before the fusion, whose epilogue reads the mimic rows; then part B (grouping), joined by
+// table_updates.
 // cu_events (optional): ttamm_step_args.timing_events + 8 — [0, 1] around the user tower's
 // catch-up replay, [2, 3] around the item tower's (overlapped: [0, 1] around the one replay of
 // both towers' lists)
 int prepare_forward(const ttamm_tower* T[2], TowerWs* W[2], int n, const ttamm_batch& bt, int D, bool mimic,
-                    const Deferred& df, hipStream_t s, hipStream_t aux, void* const* l0_events,
+                    const Deferred& df, const StreamPlan& pl, void* const* l0_events,
                     void* const* maint_events = nullptr, void* const* cu_events = nullptr,
                     void* const* gather_events = nullptr) {
     int rc;
+    const hipStream_t s = pl.s, aux = pl.aux;
+    const hipEvent_t* ev = pl.ev;
     auto cu_ev = [&](int k) -> void* const* {
         return cu_events ? cu_events + (W[k]->role == ROLE_USER ? 0 : 2) : nullptr;
     };
-    if (!overlapped(T, n, df, s, aux)) {
+    if (!pl.fork) {
         for (int k = 0; k < n; ++k)
             if ((rc = tower_prepare(*T[k], *W[k], mimic, df, s, cu_ev(k)))) return rc;
         return tower_forward(T, W, bt, D, mimic, s, n, l0_events, FWD_ALL);
     }
     // The MLP launches are enqueued first: the prologue is a dozen small launches whose
     // host-side enqueue would otherwise hold the GEMMs back behind the host.
-    hipEvent_t ev[kAuxEvents];
-    if ((rc = aux_events(ev, aux))) return rc;
-    // bf16 towers: the prologue starts after the first layer's GEMM (its one-block-per-CU tiles
-    // otherwise wait for CUs behind the catch-up replay); fp32 towers: at once
-    const bool late_fork = T[0]->matmul_bf16 && dev_env("TTAMM_EARLY_FORK") == nullptr;
     // fp32 towers: the ID-row gather also runs on the aux stream (ahead of the catch-up), beside the
     // first-layer GEMM, which reads only the feature rows; the fusion joins it with the catch-up
-    static const bool gather_main = dev_env("TTAMM_GATHER_MAIN") != nullptr;
-    const bool gather_aux = !late_fork && !gather_main;
-    if (!late_fork) TTAMM_HIP(hipEventRecord(ev[0], s));
+    const bool gather_aux = !pl.late_fork;
+    if (!pl.late_fork) TTAMM_HIP(hipEventRecord(ev[EV_FORK], s));
     if ((rc = tower_forward(T, W, bt, D, mimic, s, n, l0_events, gather_aux ? FWD_FEAT : FWD_MLP,
-                            late_fork ? ev[0] : nullptr)))
+                            pl.late_fork ? ev[EV_FORK] : nullptr)))
         return rc;
-    TTAMM_HIP(hipStreamWaitEvent(aux, ev[0], 0));
+    TTAMM_HIP(hipStreamWaitEvent(aux, ev[EV_FORK], 0));
     if (gather_aux) {
         const bool timed = gather_events && gather_events[0] && gather_events[1];
         if (timed) TTAMM_HIP(hipEventRecord((hipEvent_t)gather_events[0], aux));
@@ -1314,32 +1306,29 @@ int prepare_forward(const ttamm_tower* T[2], TowerWs* W[2], int n, const ttamm_b
         if (timed) TTAMM_HIP(hipEventRecord((hipEvent_t)gather_events[1], aux));
     }
     if ((rc = towers_prepare_a(T, W, n, mimic, df, aux, cu_ev(0)))) return rc;
-    TTAMM_HIP(hipEventRecord(ev[1], aux));
+    TTAMM_HIP(hipEventRecord(ev[EV_CURRENT], aux));
     // the fusion is enqueued before the grouping's dozen launches: enqueued after them, the host
     // still issued them when the GPU finished the MLP (~55 us idle per C2 step)
-    TTAMM_HIP(hipStreamWaitEvent(s, ev[1], 0));
+    TTAMM_HIP(hipStreamWaitEvent(s, ev[EV_CURRENT], 0));
     if ((rc = tower_forward(T, W, bt, D, mimic, s, n, l0_events, FWD_FUSION))) return rc;
-    for (int k = 0; k < n; ++k)
-        if ((rc = tower_prepare_b(*T[k], *W[k], aux))) return rc;
-    TTAMM_HIP(hipEventRecord(ev[2], aux));
-    if (df.slice_on_aux && !df.slice_late) {
+    for (int k = 0; k < n; ++k)  // part B
+        if ((rc = launch_coalesce_group(W[k]->idx, W[k]->R, T[k]->id.rows, W[k]->co, aux))) return rc;
+    TTAMM_HIP(hipEventRecord(ev[EV_GROUPED], aux));
+    if (pl.slice) {
         // The previous step's slice (target step - 1), behind this step's catch-up on the aux
         // stream, overlapping the main stream's GEMMs instead of closing the step.  The rows this
         // batch touches are current to step - 1 after the catch-up, so the slice skips them and
         // never races the row updates; its stamp is an atomicMax (a row update may have moved a
-        // row to `step` meanwhile).  The next step's catch-up and the flush are ordered after it.
+        // row to `step` meanwhile).  The next step's catch-up and the flush run on the aux stream
+        // too, after it, and supersede it (StreamPlan (b)).
         if ((rc = replay_slice(T, n, mimic, df, df.step - 1, 2, maint_events, aux))) return rc;
     }
     return TTAMM_OK;
 }
 
-// the row updates need the grouping (prepare part B), possibly still running on the aux stream
-int join_grouping(hipStream_t s, hipStream_t aux) {
-    if (aux == nullptr || aux == s) return TTAMM_OK;
-    hipEvent_t ev[kAuxEvents];
-    int rc;
-    if ((rc = aux_events(ev, aux))) return rc;
-    TTAMM_HIP(hipStreamWaitEvent(s, ev[2], 0));
+// the row updates on `s` need the grouping (prepare part B), which a fork left on the aux stream
+int join_grouping(const StreamPlan& pl) {
+    if (pl.fork) TTAMM_HIP(hipStreamWaitEvent(pl.s, pl.ev[EV_GROUPED], 0));
     return TTAMM_OK;
 }
 
@@ -1406,28 +1395,41 @@ void add_seg(SweepArgs& sw, const ttamm_table& tb) {
     sw.count++;
 }
 
+// What bind_rows derives from the arguments of one ABI call, for run_single and run_phases.
+struct Step {
+    const ttamm_step_args& A;
+    StepWs ws;
+    int D = 0;
+    bool mimic = false;
+    int64_t B = 0, Bg = 0;  // this call's batch, the global batch
+    int N = 0;
+    int64_t num_items = 0;
+    int64_t* neg = nullptr;  // where the sampler writes the negatives
+    const ttamm_tower* T[2] = {};
+    TowerWs* W[2] = {};  // {&ws.user, &ws.item}
+    AdamConsts ad{};
+    SparseConsts sp{};
+    Deferred df;
+    explicit Step(const ttamm_step_args& a) : A(a) {}
+};
+
 // Touched-row updates of the tables of `n` towers, then the AdamW(g=0) step of the rows the
 // batch did not touch: eagerly, one sweep over the dense-group tables and a scatter of the
 // staged touched rows; deferred, the replay of this step's 1/slices of the rows to `step`.
-int table_updates(const ttamm_tower* T[2], TowerWs* W[2], int n, int D, bool mimic, const SparseConsts& sp,
-                  const AdamConsts& ad, const Deferred& df, void* const events[2], hipStream_t s, hipStream_t aux,
-                  const float* grad_scale = nullptr) {
+// on_aux: on the aux stream, behind the grouping there (rows_beside_mlp); else on pl.s.
+int table_updates(const Step& c, const ttamm_tower* T[2], TowerWs* W[2], int n, const StreamPlan& pl, bool on_aux,
+                  void* const events[2], const float* grad_scale = nullptr) {
+    const int D = c.D;
+    const bool mimic = c.mimic;
+    const AdamConsts& ad = c.ad;
+    const Deferred& df = c.df;
+    const hipStream_t s = on_aux ? pl.aux : pl.s;
     int rc;
-    if ((rc = join_grouping(s, aux))) return rc;
-    if (df.on && df.slice_on_aux && df.slice_late) {
-        // the previous step's slice (target step - 1, as in prepare_forward), started on the aux
-        // stream now: the catch-up and the grouping before it on that stream, the row updates
-        // beside it (the rows they touch are current to step - 1, so the slice skips them)
-        hipEvent_t ev[kAuxEvents];
-        if ((rc = aux_events(ev, aux))) return rc;
-        TTAMM_HIP(hipEventRecord(ev[3], s));
-        TTAMM_HIP(hipStreamWaitEvent(aux, ev[3], 0));
-        if ((rc = replay_slice(T, n, mimic, df, df.step - 1, 2, events, aux))) return rc;
-    }
+    if (!on_aux && (rc = join_grouping(pl))) return rc;
     for (int k = 0; k < n; ++k)
-        if ((rc = tower_optimizer_rows(*T[k], *W[k], D, mimic, sp, ad, df, s, grad_scale))) return rc;
+        if ((rc = tower_optimizer_rows(*T[k], *W[k], D, mimic, c.sp, ad, df, s, grad_scale))) return rc;
     if (df.on) {
-        if (df.slice_on_aux) return TTAMM_OK;  // replayed on the aux stream (replay_slice_aux)
+        if (pl.slice) return TTAMM_OK;  // replayed on the aux stream (prepare_forward)
         return replay_slice(T, n, mimic, df, df.step, 1, events, s);
     }
     SweepArgs sw;
@@ -1494,17 +1496,16 @@ int dense_update(const ttamm_tower* T[2], TowerWs* W[2], const AdamConsts& ad, c
 }
 
 // the tables' row partials of the squared gradient norm into ws.clip_partials[1, *off)
-int clip_table_partials(const ttamm_tower* T[2], TowerWs* W[2], int D, bool mimic, const SparseConsts& sp,
-                        const AdamConsts& ad, const Deferred& df, StepWs& ws, hipStream_t s, hipStream_t aux,
-                        int* off_out) {
+int clip_table_partials(Step& c, const StreamPlan& pl, int* off_out) {
+    StepWs& ws = c.ws;
     int rc;
-    if ((rc = join_grouping(s, aux))) return rc;  // the row grouping
+    if ((rc = join_grouping(pl))) return rc;  // the row grouping
     int off = 1;
     for (int k = 0; k < 2; ++k) {
-        if (!T[k] || W[k]->R <= 0) continue;
-        const RowUpdateArgs ru = row_update_args(*T[k], *W[k], D, mimic, sp, ad, df, nullptr);
-        if ((rc = launch_rows_sumsq(ru, ws.clip_partials + off, s))) return rc;
-        off += rows_sumsq_blocks(W[k]->R, T[k]->id.dim);
+        if (c.W[k]->R <= 0) continue;
+        const RowUpdateArgs ru = row_update_args(*c.T[k], *c.W[k], c.D, c.mimic, c.sp, c.ad, c.df, nullptr);
+        if ((rc = launch_rows_sumsq(ru, ws.clip_partials + off, pl.s))) return rc;
+        off += rows_sumsq_blocks(c.W[k]->R, c.T[k]->id.dim);
     }
     TTAMM_REQUIRE(off <= ws.clip_parts, "clip: partials overflow");
     *off_out = off;
@@ -1513,38 +1514,36 @@ int clip_table_partials(const ttamm_tower* T[2], TowerWs* W[2], int D, bool mimi
 
 // clip_grad_norm_(model.parameters(), max_norm) (training.py:824-825): the global gradient norm
 // over both towers' table rows and dense tensors -> ws.clip_coef, read by the optimizer kernels
-int clip_coefficient(const ttamm_tower* T[2], TowerWs* W[2], int D, bool mimic, const SparseConsts& sp,
-                     const AdamConsts& ad, const Deferred& df, const ttamm_step_args& A, StepWs& ws, hipStream_t s,
-                     hipStream_t aux) {
+int clip_coefficient(Step& c, const StreamPlan& pl) {
+    StepWs& ws = c.ws;
     int rc;
     int off;
-    if ((rc = clip_table_partials(T, W, D, mimic, sp, ad, df, ws, s, aux, &off))) return rc;
-    if ((rc = launch_dense_sumsq(dense_args(T, W, ad, A.status, nullptr), ws.clip_partials + off, s))) return rc;
+    if ((rc = clip_table_partials(c, pl, &off))) return rc;
+    if ((rc = launch_dense_sumsq(dense_args(c.T, c.W, c.ad, c.A.status, nullptr), ws.clip_partials + off, pl.s)))
+        return rc;
     off += kDenseSumsqBlocks;
     TTAMM_REQUIRE(off <= ws.clip_parts, "clip: partials overflow");
-    return launch_clip_coef(ws.clip_partials + 1, off - 1, (float)A.hp.grad_clip_norm, ws.clip_coef, s);
+    return launch_clip_coef(ws.clip_partials + 1, off - 1, (float)c.A.hp.grad_clip_norm, ws.clip_coef, pl.s);
 }
 
 // sharded clipping, TOWERS_BWD: this rank's share of the squared gradient norm over the table
 // rows it owns (its users', its items' — every requester's contributions to a row summed first),
 // into *A.table_sumsq for the caller's all-reduce
-int clip_table_share(const ttamm_tower* T[2], TowerWs* W[2], int D, bool mimic, const SparseConsts& sp,
-                     const AdamConsts& ad, const Deferred& df, const ttamm_step_args& A, StepWs& ws, hipStream_t s,
-                     hipStream_t aux) {
+int clip_table_share(Step& c, const StreamPlan& pl) {
     int rc;
     int off;
-    if ((rc = clip_table_partials(T, W, D, mimic, sp, ad, df, ws, s, aux, &off))) return rc;
-    return launch_sum_partials(ws.clip_partials + 1, off - 1, A.table_sumsq, s);
+    if ((rc = clip_table_partials(c, pl, &off))) return rc;
+    return launch_sum_partials(c.ws.clip_partials + 1, off - 1, c.A.table_sumsq, pl.s);
 }
 
 // sharded clipping, TABLES: clip_grad_norm_'s coefficient from the all-reduced table share and the
 // (all-reduced) replicated-weight gradients
-int clip_coefficient_sharded(const ttamm_tower* T[2], TowerWs* W[2], const AdamConsts& ad, const ttamm_step_args& A,
-                             StepWs& ws, hipStream_t s) {
+int clip_coefficient_sharded(Step& c, hipStream_t s) {
+    StepWs& ws = c.ws;
     int rc;
-    TTAMM_HIP(hipMemcpyAsync(ws.clip_partials, A.table_sumsq, sizeof(float), hipMemcpyDeviceToDevice, s));
-    if ((rc = launch_dense_sumsq(dense_args(T, W, ad, A.status, nullptr), ws.clip_partials + 1, s))) return rc;
-    return launch_clip_coef(ws.clip_partials, 1 + kDenseSumsqBlocks, (float)A.hp.grad_clip_norm, ws.clip_coef, s);
+    TTAMM_HIP(hipMemcpyAsync(ws.clip_partials, c.A.table_sumsq, sizeof(float), hipMemcpyDeviceToDevice, s));
+    if ((rc = launch_dense_sumsq(dense_args(c.T, c.W, c.ad, c.A.status, nullptr), ws.clip_partials + 1, s))) return rc;
+    return launch_clip_coef(ws.clip_partials, 1 + kDenseSumsqBlocks, (float)c.A.hp.grad_clip_norm, ws.clip_coef, s);
 }
 
 // Deferred mode is all-or-nothing over the dense-group tables of both towers.
@@ -1578,8 +1577,13 @@ int deferred_of(const ttamm_step_args& A, Deferred& df) {
 
 // the category-alignment rows of this step: one process, the item tower's augmented rows
 // [positives; negatives]; sharded requester, its requests' (t | a) exchange rows and global ids
-CalArgs& bind_cal(const ttamm_step_args& A, StepWs& ws, const TowerWs& I, int64_t B, int D, bool mimic) {
-    CalArgs& c = ws.cal;
+CalArgs& bind_cal(Step& st) {
+    const ttamm_step_args& A = st.A;
+    const TowerWs& I = st.ws.item;
+    const int64_t B = st.B;
+    const int D = st.D;
+    const bool mimic = st.mimic;
+    CalArgs& c = st.ws.cal;
     c.xa_rows = INT64_MAX;
     if (sharded(A)) {
         c.x = A.item_fwd_in;
@@ -1606,6 +1610,132 @@ CalArgs& bind_cal(const ttamm_step_args& A, StepWs& ws, const TowerWs& I, int64_
     c.major = A.major_category;
     c.lambda = (float)A.hp.lambda_category_alignment;
     return c;
+}
+
+// ... and where their gradient goes: one process, the item tower's dT / dA; sharded requester, the
+// (dT | dA) rows it ships back
+CalArgs& bind_cal_grads(Step& st) {
+    const ttamm_step_args& A = st.A;
+    const int D = st.D;
+    CalArgs& c = bind_cal(st);
+    if (sharded(A)) {
+        c.dT = A.item_bwd_out;
+        c.dA = st.mimic ? A.item_bwd_out + D : nullptr;
+        c.ld_d = 2 * D;
+        c.dA_rows = c.R;  // every request ships its own dA
+        if (compact_exchange(A)) {  // only the positives ship a dA
+            c.ld_d = D;
+            c.dA_rows = st.B;
+        }
+    } else {
+        c.dT = st.ws.item.dT_own;
+        c.dA = st.mimic ? st.ws.item.dA_own : nullptr;
+        c.ld_d = D;
+        c.dA_rows = st.B;
+    }
+    return c;
+}
+
+// in-batch negatives: the positives every user is scored against; the BCE terms of the step
+int64_t inbatch_cols(const Step& st) { return st.ws.ib_on ? (sharded(st.A) ? st.Bg : st.B) : 0; }
+int64_t bce_count(const Step& st) { return st.Bg * ((st.ws.ib_on ? inbatch_cols(st) : 1) + st.N); }
+
+// S = U P^T, its BCE, dU and dP: one process against the batch's own positives, sharded against
+// every rank's (inbatch_items)
+InBatchArgs& bind_inbatch(Step& st) {
+    const ttamm_step_args& A = st.A;
+    const bool shard = sharded(A);
+    const int D = st.D;
+    InBatchArgs& a = st.ws.ib;
+    a.U = st.ws.user.aug;
+    a.ldu = D;
+    a.B = st.B;
+    a.P = shard ? A.inbatch_items : st.ws.item.aug;  // one process: rows [0, B), the positives
+    a.dP = shard ? A.inbatch_dp_all : st.ws.ib_dp;
+    a.ldp = D;
+    a.ld_dp = D;
+    a.Bc = inbatch_cols(st);
+    a.D = D;
+    a.row_base = shard ? A.row_base : 0;
+    a.inv_T = 1.0f / (float)(st.Bg * (inbatch_cols(st) + st.N));
+    a.dU = st.ws.ib_du;
+    a.ld_du = D;
+    return a;
+}
+int run_inbatch(Step& st, hipStream_t s) {
+    int rc;
+    void* const* ev = st.A.timing_events + 4;
+    if (ev[0] && ev[1]) TTAMM_HIP(hipEventRecord((hipEvent_t)ev[0], s));
+    if ((rc = launch_inbatch(bind_inbatch(st), s))) return rc;
+    if (ev[0] && ev[1]) TTAMM_HIP(hipEventRecord((hipEvent_t)ev[1], s));
+    return TTAMM_OK;
+}
+
+// scores, BCE and mimic MSE with their gradient seeds: one process on the item tower's rows,
+// sharded requester on the exchange rows it received / ships back
+ScoreArgs bind_score(Step& st) {
+    const ttamm_step_args& A = st.A;
+    const TowerWs &U = st.ws.user, &I = st.ws.item;
+    const int D = st.D;
+    const bool mimic = st.mimic;
+    ScoreArgs sa;
+    std::memset(&sa, 0, sizeof(sa));
+    sa.B = st.B;
+    sa.Bg = st.Bg;
+    sa.N = st.N;
+    sa.D = D;
+    sa.user_aug = U.aug;
+    sa.t_user = U.t;
+    sa.a_user = U.a;
+    sa.lambda_u = (float)A.hp.lambda_mimic_user;
+    sa.lambda_i = (float)A.hp.lambda_mimic_item;
+    sa.mimic = mimic ? 1 : 0;
+    sa.dT_user = U.dT_own;
+    sa.dA_user = U.dA_own;
+    if (sharded(A)) {
+        sa.item_aug = nullptr;
+        sa.t_item = A.item_fwd_in;
+        sa.a_item = mimic ? A.item_fwd_in + D : nullptr;
+        sa.ld_item = 2 * D;
+        sa.dT_item = A.item_bwd_out;
+        sa.dA_item = mimic ? A.item_bwd_out + D : nullptr;
+        sa.dA_all = 1;
+        sa.ld_dti = 2 * D;
+        sa.item_slot = A.item_slot;
+        if (compact_exchange(A)) {  // D-float units; negatives: t + a in, dT out (their dA is dT)
+            sa.ld_item = sa.ld_dti = D;
+            sa.dA_all = 0;
+            sa.neg_aug = 1;
+        }
+    } else {
+        sa.item_aug = I.aug;
+        sa.t_item = I.t;
+        sa.a_item = I.a;
+        sa.ld_item = D;
+        sa.dT_item = I.dT_own;
+        sa.dA_item = I.dA_own;
+        sa.ld_dti = D;
+    }
+    sa.partials = st.ws.partials;
+    sa.blocks = st.ws.score_blocks;
+    sa.inv_numel = 1.0f / (float)bce_count(st);
+    if (st.ws.ib_on) {
+        sa.ib_du = st.ws.ib_du;
+        sa.ib_dp = sharded(A) ? A.inbatch_dp : st.ws.ib_dp;
+        sa.ib_ld = D;
+    }
+    return sa;
+}
+
+int loss_finalize(const Step& st, hipStream_t s) {
+    const ttamm_step_args& A = st.A;
+    const StepWs& ws = st.ws;
+    if (!A.loss_out) return TTAMM_OK;
+    return launch_loss_finalize(ws.partials, ws.score_blocks, ws.ib_on ? ws.ib.loss_part : nullptr,
+                                ws.ib_on ? ws.ib_parts : 0, bce_count(st), st.B, st.Bg, st.D,
+                                (float)A.hp.lambda_mimic_user, (float)A.hp.lambda_mimic_item, st.mimic ? 1 : 0,
+                                ws.cal_on && A.row_base == 0 ? ws.cal.out : nullptr,
+                                (float)A.hp.lambda_category_alignment, A.loss_out, A.loss_accum, A.status, s);
 }
 
 int validate_step(const ttamm_step_args& A) {
@@ -1696,34 +1826,33 @@ int validate_step(const ttamm_step_args& A) {
     return TTAMM_OK;
 }
 
-int run_step(const ttamm_step_args& A, hipStream_t s) {
+// The shared preamble of a step call: validate, lay out the workspace, bind the towers' rows to
+// it (sharded: the item tower's to the caller's exchange buffers), form the optimizers' constants.
+int bind_rows(Step& c) {
+    const ttamm_step_args& A = c.A;
     int rc;
     if ((rc = validate_step(A))) return rc;
-    const int D = out_dim(A.user);
-    const bool mimic = A.mimic_enabled != 0;
+    const int D = c.D = out_dim(A.user);
+    const bool mimic = c.mimic = A.mimic_enabled != 0;
     const bool shard = sharded(A);
-    const int ph = shard ? A.phase : 255;
 
     Arena ar{static_cast<char*>(A.workspace), A.workspace_bytes, 0, false};
-    StepWs ws;
-    plan(ar, A, ws);
+    plan(ar, A, c.ws);
     TTAMM_REQUIRE(ar.ok(), "workspace too small for this step");
 
-    const int64_t B = A.b.batch;
-    const int N = A.b.num_neg;
-    const int64_t Bg = global_batch(A);
-    const int64_t num_items = A.num_items_global > 0 ? A.num_items_global : A.item.id.rows;
-    // ---- row bindings -----------------------------------------------------------------------
-    TowerWs& U = ws.user;
-    TowerWs& I = ws.item;
+    const int64_t B = c.B = A.b.batch;
+    const int N = c.N = A.b.num_neg;
+    const int64_t Bg = c.Bg = global_batch(A);
+    c.num_items = A.num_items_global > 0 ? A.num_items_global : A.item.id.rows;
+    TowerWs& U = c.ws.user;
+    TowerWs& I = c.ws.item;
     U.idx = U.fidx = U.idx_own;  // staged copy of A.b.users
     U.key_split = B;
     U.key_base0 = A.row_base;
-    int64_t* neg = nullptr;
     if (shard) {
         I.R = A.n_item_rows;
         I.idx = I.fidx = I.idx_own;  // staged copy of A.item_rows
-        I.row_key = ws.keys_own;  // staged copy of A.item_row_keys (ITEM_FWD)
+        I.row_key = c.ws.keys_own;  // staged copy of A.item_row_keys (ITEM_FWD)
         I.t = A.item_fwd_out;
         I.a = mimic && A.item_fwd_out ? A.item_fwd_out + D : nullptr;
         I.t_ld = 2 * D;
@@ -1735,384 +1864,262 @@ int run_step(const ttamm_step_args& A, hipStream_t s) {
         I.dA_split = I.R;  // every row's mimic gradient is shipped in (dT | dA)
         if (compact_exchange(A)) {  // D-float units: (t | a) of a positive, t + a of a negative
             I.t_ld = I.dT_ld = I.dA_ld = D;
-            I.xu = ws.own_units;
+            I.xu = c.ws.own_units;
         }
         I.renorm_key_split = Bg;  // request keys: positives [0, Bg), negatives from Bg on
-        neg = A.b.neg_items;
+        c.neg = A.b.neg_items;
     } else {
         I.idx = I.fidx = I.idx_own;
         // item row r < B is interaction r's positive, else negative slot r - B
         I.key_split = B;
         I.key_base0 = A.row_base;
         I.key_base1 = Bg + A.row_base * N;
-        neg = I.idx_own + B;
+        c.neg = I.idx_own + B;
+        I.renorm_split = B;
     }
     // max_norm claim tags: unique per lookup (users; positives, then negatives)
     U.renorm_tag = I.renorm_tag = (int32_t)(2 * (A.hp.dense_step % (1 << 29)) + 1);
-    if (!shard) I.renorm_split = B;
-    const ttamm_tower* T[2] = {&A.user, &A.item};
-    TowerWs* W[2] = {&U, &I};
-    // TTAMM_PROLOGUE_PREP=1: the SAMPLE phase's prologue forms the first-layer weights (every step
-    // runs it first) instead of the pad / bf16 launches before the first GEMM.  Measured slower at
-    // C2 (0.660 vs 0.648 ms/step, two A/B pairs on one box; C5 unchanged at 1.413 ms,
-    // profiles/r05_s9_prologue_prep.txt): the first GEMM waits for the whole prologue grid
-    {
-        const char* e = dev_env("TTAMM_PROLOGUE_PREP");
-        U.weight_prepped = I.weight_prepped = e && e[0] == '1';
-    }
+    c.T[0] = &A.user, c.T[1] = &A.item;
+    c.W[0] = &U, c.W[1] = &I;
     const ttamm_hparams& hp = A.hp;
-    AdamConsts ad = hp.dense_optimizer == TTAMM_DENSE_SGD
-                        ? make_sgd_consts(hp.lr, hp.weight_decay, hp.momentum, hp.dampening, hp.nesterov,
-                                          hp.sgd_first_step)
-                        : make_adam_consts(hp.lr, hp.beta1, hp.beta2, hp.eps, hp.weight_decay,
-                                           hp.decoupled_weight_decay, hp.dense_step);
-    ad.fast_g0 = A.table_g0_math == TTAMM_G0_FAST ? 1 : 0;
-    const SparseConsts sp = make_sparse_consts(hp.sparse_lr, hp.sparse_beta1, hp.sparse_beta2, hp.sparse_eps,
-                                               hp.sparse_step);
-    Deferred df;
-    if ((rc = deferred_of(A, df))) return rc;
-    df.status = A.status;
+    c.ad = hp.dense_optimizer == TTAMM_DENSE_SGD
+               ? make_sgd_consts(hp.lr, hp.weight_decay, hp.momentum, hp.dampening, hp.nesterov, hp.sgd_first_step)
+               : make_adam_consts(hp.lr, hp.beta1, hp.beta2, hp.eps, hp.weight_decay, hp.decoupled_weight_decay,
+                                  hp.dense_step);
+    c.ad.fast_g0 = A.table_g0_math == TTAMM_G0_FAST ? 1 : 0;
+    c.sp = make_sparse_consts(hp.sparse_lr, hp.sparse_beta1, hp.sparse_beta2, hp.sparse_eps, hp.sparse_step);
+    if ((rc = deferred_of(A, c.df))) return rc;
+    c.df.status = A.status;
+    return TTAMM_OK;
+}
 
-    // ---- indices and negatives ---------------------------------------------------------------
-    // one process with the aux stream: the step's count / AdamW constants on the aux stream (below;
-    // not with the developer's slice on the main stream, which replays to this step's entry)
-    const bool begin_aux = !shard && (ph & TTAMM_PHASE_SAMPLE) &&
-                           overlapped(T, 2, df, s, static_cast<hipStream_t>(A.aux_stream)) &&
-                           !dev_env("TTAMM_SLICE_MAIN");
-    if (ph & TTAMM_PHASE_SAMPLE) {
-        // range-checked copies of the batch's ids (nn.Embedding raises IndexError,
-        // encoders.py:222-223): an out-of-range id sets TTAMM_STATUS_INDEX_OUT_OF_RANGE, is
-        // replaced by row 0 so no kernel reads outside a table, and the step writes nothing
-        StageArgs st;
-        std::memset(&st, 0, sizeof(st));
-        st.status = A.status;
-        st.seg[st.count++] = StageSeg{A.b.users, U.idx_own, B, A.user.id.rows};
-        if (!shard) {
-            st.seg[st.count++] = StageSeg{A.b.pos_items, I.idx_own, B, A.item.id.rows};
-            if (!A.b.sample_negatives && N > 0) {
-                TTAMM_REQUIRE(A.b.neg_items != nullptr, "negatives must be given when sample_negatives == 0");
-                st.seg[st.count++] = StageSeg{A.b.neg_items, neg, B * N, A.item.id.rows};
-            }
-        } else {  // requester: global item ids, checked only (the owners stage their local rows)
-            st.seg[st.count++] = StageSeg{A.b.pos_items, nullptr, B, num_items};
-            if (!A.b.sample_negatives && A.b.neg_items && N > 0)
-                st.seg[st.count++] = StageSeg{A.b.neg_items, nullptr, B * N, num_items};
+// Indices and negatives: range-checked copies of the batch's ids (nn.Embedding raises IndexError,
+// encoders.py:222-223: an out-of-range id sets TTAMM_STATUS_INDEX_OUT_OF_RANGE, is replaced by
+// row 0 so no kernel reads outside a table, and the step writes nothing), the sampler and —
+// begin_here — the step's count + AdamW constants (unless a status error stops it), in one launch.
+// !begin_here: the caller runs launch_step_begin on the aux stream instead.
+int step_prologue(Step& c, bool begin_here, hipStream_t s) {
+    const ttamm_step_args& A = c.A;
+    const bool shard = sharded(A);
+    const int64_t B = c.B;
+    const int N = c.N;
+    StageArgs st;
+    std::memset(&st, 0, sizeof(st));
+    st.status = A.status;
+    st.seg[st.count++] = StageSeg{A.b.users, c.ws.user.idx_own, B, A.user.id.rows};
+    if (!shard) {
+        st.seg[st.count++] = StageSeg{A.b.pos_items, c.ws.item.idx_own, B, A.item.id.rows};
+        if (!A.b.sample_negatives && N > 0) {
+            TTAMM_REQUIRE(A.b.neg_items != nullptr, "negatives must be given when sample_negatives == 0");
+            st.seg[st.count++] = StageSeg{A.b.neg_items, c.neg, B * N, A.item.id.rows};
         }
-        TTAMM_REQUIRE(A.status != nullptr, "the training step needs a status word");
-        // staging, the sampler and the step's count + AdamW constants (unless a status error
-        // stops it) in one launch
-        TTAMM_REQUIRE(!(A.b.sample_negatives && N > 0) || num_items > 1, "num_items must be greater than one.");
-        PrologueArgs pa;
-        std::memset(&pa, 0, sizeof(pa));
-        if (A.b.sample_negatives && N > 0) {
-            // one process: into the item tower's rows and (when given) the caller's buffer
-            pa.users = A.b.users;
-            pa.user_rows = A.user.id.rows;
-            pa.batch = B;
-            pa.num_neg = N;
-            pa.num_items = (uint64_t)num_items;
-            pa.pos_offsets = A.b.pos_offsets;
-            pa.pos_values = A.b.pos_values;
-            pa.k0 = (uint32_t)A.b.seed;
-            pa.k1 = (uint32_t)(A.b.seed >> 32);
-            pa.counter = A.b.counter;
-            pa.slot_base = A.row_base * N;
-            pa.out = neg;
-            pa.out2 = (!shard && A.b.neg_items != neg) ? A.b.neg_items : nullptr;
-        }
-        pa.done = ws.prologue_done;
-        // the first feature layer's weight in its GEMM's layout, in this launch (both towers; every
-        // later phase of the step reads it: tower_forward skips its own pad / bf16 launches)
-        for (int k = 0; k < 2; ++k) {
-            const ttamm_tower& t = *T[k];
-            TowerWs& w = *W[k];
-            if (t.fusion == TTAMM_FUSION_IDENTITY || t.n_linear == 0 || !w.weight_prepped) continue;
-            const ttamm_linear& L = t.linear[0];
-            if (w.w16)
-                pa.prep[pa.n_prep++] = WeightPrep{L.weight, L.out_features, L.in_features, L.in_features, w.w16,
-                                                  round8(L.in_features), 1};
-            else if (w.wpad)
-                pa.prep[pa.n_prep++] = WeightPrep{L.weight, L.out_features, L.in_features, L.in_features, w.wpad,
-                                                  round4(L.in_features), 0};
-        }
-        pa.applied = A.steps_applied;
-        pa.hist = df.on ? df.hist : nullptr;
-        pa.cap = df.on ? df.cap : 2;
-        pa.step = df.step;
-        pa.c = ad;
-        // one process with the aux stream: the step's count and AdamW constants are published by
-        // step_begin_kernel on the aux stream (after the fork, below) instead of by the prologue's
-        // last block — its completion counter (a release fence and an atomic per block) sat on the
-        // main stream's path to the first GEMM.  Nothing in this step reads this step's history
-        // entry (the catch-up and the rolling slice replay to step - 1); the next step's catch-up
-        // and the flush are ordered after it on the aux stream or after the step's join.
-        if (begin_aux) {
-            pa.applied = nullptr;
-            pa.hist = nullptr;
-            pa.done = nullptr;
-        }
-        if ((rc = launch_step_prologue(st, pa, s))) return rc;
+    } else {  // requester: global item ids, checked only (the owners stage their local rows)
+        st.seg[st.count++] = StageSeg{A.b.pos_items, nullptr, B, c.num_items};
+        if (!A.b.sample_negatives && A.b.neg_items && N > 0)
+            st.seg[st.count++] = StageSeg{A.b.neg_items, nullptr, B * N, c.num_items};
     }
-    if (shard && (ph & TTAMM_PHASE_ITEM_FWD) && I.R > 0) {
-        // owner: stage the requested local rows (range-checked) and their keys, contiguous
+    TTAMM_REQUIRE(A.status != nullptr, "the training step needs a status word");
+    TTAMM_REQUIRE(!(A.b.sample_negatives && N > 0) || c.num_items > 1, "num_items must be greater than one.");
+    PrologueArgs pa;
+    std::memset(&pa, 0, sizeof(pa));
+    if (A.b.sample_negatives && N > 0) {
+        // one process: into the item tower's rows and (when given) the caller's buffer
+        pa.users = A.b.users;
+        pa.user_rows = A.user.id.rows;
+        pa.batch = B;
+        pa.num_neg = N;
+        pa.num_items = (uint64_t)c.num_items;
+        pa.pos_offsets = A.b.pos_offsets;
+        pa.pos_values = A.b.pos_values;
+        pa.k0 = (uint32_t)A.b.seed;
+        pa.k1 = (uint32_t)(A.b.seed >> 32);
+        pa.counter = A.b.counter;
+        pa.slot_base = A.row_base * N;
+        pa.out = c.neg;
+        pa.out2 = (!shard && A.b.neg_items != c.neg) ? A.b.neg_items : nullptr;
+    }
+    pa.cap = c.df.on ? c.df.cap : 2;
+    pa.step = c.df.step;
+    pa.c = c.ad;
+    if (begin_here) {
+        pa.done = c.ws.prologue_done;
+        pa.applied = A.steps_applied;
+        pa.hist = c.df.on ? c.df.hist : nullptr;
+    }
+    return launch_step_prologue(st, pa, s);
+}
+
+// The backward of both towers with the touched-row updates on the aux stream (pl.rows): once the
+// fusion backward has formed the ID and mimic rows' gradients, the row updates run there beside
+// the MLP's dgrad chain and weight gradients (memory-bound row traffic under MFMA-bound GEMMs).
+// The grouping precedes them on that stream already.  The last operation joins the aux stream, so
+// what follows the call on `s` — the next step's ID-row gather, the caller's all-reduce — sees the
+// updated rows (StreamPlan (a)).  single: the one-process step, whose loss reduction (nothing in
+// the backward reads it) goes ahead of the row updates and whose dense update closes the step;
+// sharded, the DENSE phase follows the caller's all-reduce.
+int rows_beside_mlp(Step& c, const StreamPlan& pl, bool single) {
+    const ttamm_step_args& A = c.A;
+    int rc;
+    if ((rc = tower_backward(c.T, c.W, c.D, pl.s, 2, nullptr, BWD_GATE))) return rc;
+    TTAMM_HIP(hipEventRecord(pl.ev[EV_TO_AUX], pl.s));
+    TTAMM_HIP(hipStreamWaitEvent(pl.aux, pl.ev[EV_TO_AUX], 0));
+    if (single && (rc = loss_finalize(c, pl.aux))) return rc;
+    if ((rc = table_updates(c, c.T, c.W, 2, pl, true, A.timing_events))) return rc;
+    TTAMM_HIP(hipEventRecord(pl.ev[EV_FROM_AUX], pl.aux));
+    if ((rc = tower_backward(c.T, c.W, c.D, pl.s, 2, A.timing_events + 6, BWD_MLP))) return rc;
+    if (single && (rc = dense_update(c.T, c.W, c.ad, A.status, pl.s))) return rc;
+    TTAMM_HIP(hipStreamWaitEvent(pl.s, pl.ev[EV_FROM_AUX], 0));
+    return TTAMM_OK;
+}
+
+// ---- the one-process step, in launch order ------------------------------------------------------
+int run_single(Step& c, const StreamPlan& pl) {
+    const ttamm_step_args& A = c.A;
+    const Deferred& df = c.df;
+    StepWs& ws = c.ws;
+    const hipStream_t s = pl.s;
+    int rc;
+    // pl.rows: the step's count and AdamW constants are published by step_begin_kernel on the aux
+    // stream (below) instead of by the prologue's last block, whose completion counter (a release
+    // fence and an atomic per block) sat on the main stream's path to the first GEMM.  Nothing in
+    // this step reads this step's history entry (the catch-up and the rolling slice replay to
+    // step - 1), and the join of the row updates at the step's end covers it.
+    if ((rc = step_prologue(c, !pl.rows, s))) return rc;
+    if ((rc = prepare_forward(c.T, c.W, 2, A.b, c.D, c.mimic, df, pl, A.timing_events + 2, A.timing_events,
+                              A.timing_events + 8, A.timing_events + 12)))
+        return rc;
+    if (pl.rows && (rc = launch_step_begin(A.status, A.steps_applied, df.on ? df.hist : nullptr, df.on ? df.cap : 2,
+                                           df.step, c.ad, pl.aux)))
+        return rc;
+    if (ws.ib_on && (rc = run_inbatch(c, s))) return rc;
+    // score + loss (fwd + bwd seeds), + lambda * L_cal over cat[positives; negatives]
+    // (training.py:805-820)
+    if ((rc = launch_score_loss(bind_score(c), s))) return rc;
+    if (ws.cal_on && (rc = launch_category_alignment(bind_cal_grads(c), s))) return rc;
+    if (pl.rows) return rows_beside_mlp(c, pl, true);
+    // one stream, or clipping (the table updates wait for the global norm)
+    if ((rc = loss_finalize(c, s))) return rc;
+    if ((rc = tower_backward(c.T, c.W, c.D, s, 2, A.timing_events + 6))) return rc;
+    if (ws.clip_on && (rc = clip_coefficient(c, pl))) return rc;
+    if ((rc = table_updates(c, c.T, c.W, 2, pl, false, A.timing_events, ws.clip_coef))) return rc;
+    return dense_update(c.T, c.W, c.ad, A.status, s, ws.clip_coef);
+}
+
+// ---- the row-sharded step's phases (ttamm.h TTAMM_PHASE_*), in the order their bits execute -----
+// ITEM_FWD / USER_FWD: the owner stages the requested local rows (range-checked) and their keys,
+// contiguous, then the towers' forward — both in one grouped pass when the call asks for both
+int phase_forward(Step& c, const StreamPlan& pl) {
+    const ttamm_step_args& A = c.A;
+    TowerWs& I = c.ws.item;
+    const hipStream_t s = pl.s;
+    const int ph = A.phase;
+    int rc;
+    if ((ph & TTAMM_PHASE_ITEM_FWD) && I.R > 0) {
         StageArgs st;
         std::memset(&st, 0, sizeof(st));
         st.status = A.status;
         st.seg[st.count++] = StageSeg{A.item_rows, I.idx_own, I.R, A.item.id.rows, A.item_rows_ld};
-        st.seg[st.count++] = StageSeg{A.item_row_keys, ws.keys_own, I.R, INT64_MAX, A.item_rows_ld};
+        st.seg[st.count++] = StageSeg{A.item_row_keys, c.ws.keys_own, I.R, INT64_MAX, A.item_rows_ld};
         if (compact_exchange(A)) {  // ... and their exchange units (requester groups as they arrived)
             st.unit_counts = A.exchange_counts + (int64_t)A.exchange_world * A.exchange_counts_ld;
             st.unit_ld = A.exchange_counts_ld;
             st.unit_groups = A.exchange_world;
             st.unit_n = I.R;
-            st.unit_out = ws.own_units;
+            st.unit_out = c.ws.own_units;
         }
         if ((rc = launch_stage_rows(st, s))) return rc;
     }
-    // ---- forward ----------------------------------------------------------------------------
-    hipStream_t aux = static_cast<hipStream_t>(A.aux_stream);
-    if (!shard) {
-        df.slice_on_aux = df.on && overlapped(T, 2, df, s, aux) && !dev_env("TTAMM_SLICE_MAIN");
-        df.slice_late = df.slice_on_aux && dev_env("TTAMM_SLICE_LATE") != nullptr;
-        if ((rc = prepare_forward(T, W, 2, A.b, D, mimic, df, s, aux, A.timing_events + 2, A.timing_events,
-                                  A.timing_events + 8, A.timing_events + 12)))
-            return rc;
-        if (begin_aux && (rc = launch_step_begin(A.status, A.steps_applied, df.on ? df.hist : nullptr,
-                                                 df.on ? df.cap : 2, df.step, ad, aux)))
-            return rc;
-    } else {
-        const ttamm_tower* Ti[2] = {&A.item, nullptr};
-        TowerWs* Wi[2] = {&I, nullptr};
-        const int both = TTAMM_PHASE_ITEM_FWD | TTAMM_PHASE_USER_FWD;
-        if ((ph & both) == both && I.R > 0) {  // grouped: both towers' launches at once
-            if ((rc = prepare_forward(T, W, 2, A.b, D, mimic, df, s, aux, A.timing_events + 2, nullptr,
+    const ttamm_tower* Ti[2] = {&A.item, nullptr};
+    TowerWs* Wi[2] = {&I, nullptr};
+    const int both = TTAMM_PHASE_ITEM_FWD | TTAMM_PHASE_USER_FWD;
+    if ((ph & both) == both && I.R > 0)  // grouped: both towers' launches at once
+        return prepare_forward(c.T, c.W, 2, A.b, c.D, c.mimic, c.df, pl, A.timing_events + 2, nullptr,
+                               A.timing_events + 8);
+    if (ph & TTAMM_PHASE_ITEM_FWD) {
+        if (I.R > 0) {
+            if ((rc = prepare_forward(Ti, Wi, 1, A.b, c.D, c.mimic, c.df, pl, A.timing_events + 2, nullptr,
                                       A.timing_events + 8)))
                 return rc;
-        } else if (ph & TTAMM_PHASE_ITEM_FWD) {
-            if (I.R > 0) {
-                if ((rc = prepare_forward(Ti, Wi, 1, A.b, D, mimic, df, s, aux, A.timing_events + 2, nullptr,
-                                          A.timing_events + 8)))
-                    return rc;
-            } else if ((rc = tower_prepare(A.item, I, mimic, df, s))) {
-                return rc;
-            }
+        } else if ((rc = tower_prepare(A.item, I, c.mimic, c.df, s))) {
+            return rc;
         }
-        if ((ph & TTAMM_PHASE_USER_FWD) && !((ph & both) == both && I.R > 0))
-            if ((rc = prepare_forward(T, W, 1, A.b, D, mimic, df, s, aux, nullptr, nullptr, A.timing_events + 8)))
-                return rc;
     }
-    // ---- in-batch negatives: S = U P^T, its BCE, dU and dP ------------------------------------
-    const int64_t ib_cols = ws.ib_on ? (shard ? Bg : B) : 0;  // positives every user is scored against
-    if (ws.ib_on && shard && (ph & TTAMM_PHASE_INBATCH_SRC)) {
+    if (ph & TTAMM_PHASE_USER_FWD)
+        return prepare_forward(c.T, c.W, 1, A.b, c.D, c.mimic, c.df, pl, nullptr, nullptr, A.timing_events + 8);
+    return TTAMM_OK;
+}
+
+// no requests: this rank's item-tower gradient share is zero
+int zero_item_grads(Step& c, hipStream_t s) {
+    TowerWs& I = c.ws.item;
+    const size_t n = tower_grad_floats(c.A.item);
+    if (n) TTAMM_HIP(hipMemsetAsync(I.gw[0] ? I.gw[0] : I.ggw[0], 0, n * sizeof(float), s));
+    return TTAMM_OK;
+}
+
+int run_phases(Step& c, const StreamPlan& pl) {
+    const ttamm_step_args& A = c.A;
+    StepWs& ws = c.ws;
+    TowerWs& I = ws.item;
+    const int D = c.D;
+    const hipStream_t s = pl.s;
+    const int ph = A.phase;
+    const ttamm_tower* Ti[2] = {&A.item, nullptr};
+    TowerWs* Wi[2] = {&I, nullptr};
+    int rc;
+    // ---- SAMPLE: the step's count and AdamW constants always with the prologue, on `s`
+    if ((ph & TTAMM_PHASE_SAMPLE) && (rc = step_prologue(c, true, s))) return rc;
+    // ---- ITEM_FWD / USER_FWD
+    if ((ph & (TTAMM_PHASE_ITEM_FWD | TTAMM_PHASE_USER_FWD)) && (rc = phase_forward(c, pl))) return rc;
+    // ---- INBATCH_SRC: this rank's positives' augmented rows for the all-gather
+    if (ws.ib_on && (ph & TTAMM_PHASE_INBATCH_SRC)) {
         TTAMM_REQUIRE(A.item_fwd_in && A.inbatch_local, "INBATCH_SRC needs item_fwd_in and inbatch_local");
         const bool cx = compact_exchange(A);  // positives keep (t | a) in either layout
-        if ((rc = launch_add_rows(A.item_fwd_in, cx ? D : 2 * D, mimic ? A.item_fwd_in + D : nullptr, cx ? D : 2 * D,
-                                  B, D, A.inbatch_local, D, s, A.item_slot)))
+        if ((rc = launch_add_rows(A.item_fwd_in, cx ? D : 2 * D, c.mimic ? A.item_fwd_in + D : nullptr,
+                                  cx ? D : 2 * D, c.B, D, A.inbatch_local, D, s, A.item_slot)))
             return rc;
     }
-    if (ws.ib_on && (ph & (shard ? TTAMM_PHASE_INBATCH : TTAMM_PHASE_USER))) {
-        InBatchArgs& a = ws.ib;
-        a.U = U.aug;
-        a.ldu = D;
-        a.B = B;
-        if (shard) {
-            TTAMM_REQUIRE(A.inbatch_items && A.inbatch_dp_all, "INBATCH needs inbatch_items and inbatch_dp_all");
-            a.P = A.inbatch_items;
-            a.dP = A.inbatch_dp_all;
-        } else {
-            a.P = I.aug;  // rows [0, B): the positives
-            a.dP = ws.ib_dp;
-        }
-        a.ldp = D;
-        a.ld_dp = D;
-        a.Bc = ib_cols;
-        a.D = D;
-        a.row_base = shard ? A.row_base : 0;
-        a.inv_T = 1.0f / (float)(Bg * (ib_cols + N));
-        a.dU = ws.ib_du;
-        a.ld_du = D;
-        void* const* ev = A.timing_events + 4;
-        if (ev[0] && ev[1]) TTAMM_HIP(hipEventRecord((hipEvent_t)ev[0], s));
-        if ((rc = launch_inbatch(a, s))) return rc;
-        if (ev[0] && ev[1]) TTAMM_HIP(hipEventRecord((hipEvent_t)ev[1], s));
+    // ---- INBATCH: the in-batch scores against every rank's positives
+    if (ws.ib_on && (ph & TTAMM_PHASE_INBATCH)) {
+        TTAMM_REQUIRE(A.inbatch_items && A.inbatch_dp_all, "INBATCH needs inbatch_items and inbatch_dp_all");
+        if ((rc = run_inbatch(c, s))) return rc;
     }
-    // ---- sharded category alignment: global per-category sums, then centered scatters ---------
-    if (shard && ws.cal_on && (ph & TTAMM_PHASE_CAL_STATS))
-        if ((rc = launch_cal_local(bind_cal(A, ws, I, B, D, mimic), s))) return rc;
-    if (shard && ws.cal_on && (ph & TTAMM_PHASE_CAL_SCATTER))
-        if ((rc = launch_cal_scatter(bind_cal(A, ws, I, B, D, mimic), s))) return rc;
-    // ---- score + loss (fwd + bwd seeds), user-side backward ---------------------------------
+    // ---- CAL_STATS / CAL_SCATTER: global per-category sums, then centered scatters
+    if (ws.cal_on && (ph & TTAMM_PHASE_CAL_STATS) && (rc = launch_cal_local(bind_cal(c), s))) return rc;
+    if (ws.cal_on && (ph & TTAMM_PHASE_CAL_SCATTER) && (rc = launch_cal_scatter(bind_cal(c), s))) return rc;
+    // ---- USER / SCORE: score + loss (fwd + bwd seeds) against the received item rows; USER: the
+    // user-side backward and table updates with it
     if (ph & (TTAMM_PHASE_USER | TTAMM_PHASE_SCORE)) {
-        ScoreArgs sa;
-        std::memset(&sa, 0, sizeof(sa));
-        sa.B = B;
-        sa.Bg = Bg;
-        sa.N = N;
-        sa.D = D;
-        sa.user_aug = U.aug;
-        sa.t_user = U.t;
-        sa.a_user = U.a;
-        sa.lambda_u = (float)A.hp.lambda_mimic_user;
-        sa.lambda_i = (float)A.hp.lambda_mimic_item;
-        sa.mimic = mimic ? 1 : 0;
-        sa.dT_user = U.dT_own;
-        sa.dA_user = U.dA_own;
-        if (shard) {
-            sa.item_aug = nullptr;
-            sa.t_item = A.item_fwd_in;
-            sa.a_item = mimic ? A.item_fwd_in + D : nullptr;
-            sa.ld_item = 2 * D;
-            sa.dT_item = A.item_bwd_out;
-            sa.dA_item = mimic ? A.item_bwd_out + D : nullptr;
-            sa.dA_all = 1;
-            sa.ld_dti = 2 * D;
-            sa.item_slot = A.item_slot;
-            if (compact_exchange(A)) {  // D-float units; negatives: t + a in, dT out (their dA is dT)
-                sa.ld_item = sa.ld_dti = D;
-                sa.dA_all = 0;
-                sa.neg_aug = 1;
-            }
-        } else {
-            sa.item_aug = I.aug;
-            sa.t_item = I.t;
-            sa.a_item = I.a;
-            sa.ld_item = D;
-            sa.dT_item = I.dT_own;
-            sa.dA_item = I.dA_own;
-            sa.ld_dti = D;
-        }
-        sa.partials = ws.partials;
-        sa.blocks = ws.score_blocks;
-        const int64_t bce_count = Bg * ((ws.ib_on ? ib_cols : 1) + N);
-        sa.inv_numel = 1.0f / (float)bce_count;
-        if (ws.ib_on) {
-            TTAMM_REQUIRE(!shard || A.inbatch_dp, "sharded in-batch USER phase needs inbatch_dp");
-            sa.ib_du = ws.ib_du;
-            sa.ib_dp = shard ? A.inbatch_dp : ws.ib_dp;
-            sa.ib_ld = D;
-        }
-        if ((rc = launch_score_loss(sa, s))) return rc;
-        if (ws.cal_on) {  // + lambda * L_cal over cat[positives; negatives] (training.py:805-820)
-            CalArgs& c = bind_cal(A, ws, I, B, D, mimic);
-            if (shard) {
-                c.dT = A.item_bwd_out;
-                c.dA = mimic ? A.item_bwd_out + D : nullptr;
-                c.ld_d = 2 * D;
-                c.dA_rows = c.R;  // every request ships its own dA
-                if (compact_exchange(A)) {  // only the positives ship a dA
-                    c.ld_d = D;
-                    c.dA_rows = B;
-                }
-                if ((rc = launch_cal_finish(c, s))) return rc;
-            } else {
-                c.dT = I.dT_own;
-                c.dA = mimic ? I.dA_own : nullptr;
-                c.ld_d = D;
-                c.dA_rows = B;
-                if ((rc = launch_category_alignment(c, s))) return rc;
-            }
-        }
-        auto finalize = [&](hipStream_t st) {
-            return A.loss_out ? launch_loss_finalize(ws.partials, ws.score_blocks, ws.ib_on ? ws.ib.loss_part : nullptr,
-                                                     ws.ib_on ? ws.ib_parts : 0, bce_count, B, Bg, D, sa.lambda_u,
-                                                     sa.lambda_i, sa.mimic,
-                                                     ws.cal_on && A.row_base == 0 ? ws.cal.out : nullptr,
-                                                     (float)A.hp.lambda_category_alignment, A.loss_out, A.loss_accum,
-                                                     A.status, st)
-                              : TTAMM_OK;
-        };
-        // one process with the touched-row updates on the aux stream: the loss reduction (nothing in
-        // the backward reads it) goes there too, ahead of them, instead of between the scores and the
-        // fusion backward on the main stream.  TTAMM_ROWS_MAIN=1 / TTAMM_FINALIZE_MAIN=1: main stream.
-        static const bool rows_main = dev_env("TTAMM_ROWS_MAIN") != nullptr;
-        static const bool fin_main = dev_env("TTAMM_FINALIZE_MAIN") != nullptr;
-        const bool rows_aux = !shard && !ws.clip_on && !rows_main && aux != nullptr && aux != s &&
-                              overlapped(T, 2, df, s, aux);
-        const bool fin_aux = rows_aux && !fin_main;
-        if (!fin_aux && (rc = finalize(s))) return rc;
-        if (!shard) {
-            // ---- the whole backward + optimizers in one process --------------------------------
-            // With the aux stream (no clipping: the table updates would wait for the global norm)
-            // the touched-row updates run there once the fusion backward has formed the ID and
-            // mimic rows' gradients, beside the MLP's dgrad chain and weight gradients (memory-
-            // bound row traffic under MFMA-bound GEMMs); the step's end joins them, so the next
-            // step's ID-row gather reads the updated rows.  TTAMM_ROWS_MAIN=1: on the main stream.
-            if (!rows_aux) {
-                if ((rc = tower_backward(T, W, D, s, 2, A.timing_events + 6))) return rc;
-                if (ws.clip_on && (rc = clip_coefficient(T, W, D, mimic, sp, ad, df, A, ws, s, aux))) return rc;
-                if ((rc = table_updates(T, W, 2, D, mimic, sp, ad, df, A.timing_events, s, aux, ws.clip_coef)))
-                    return rc;
-                return dense_update(T, W, ad, A.status, s, ws.clip_coef);
-            }
-            hipEvent_t ev[kAuxEvents];
-            if ((rc = aux_events(ev, aux))) return rc;
-            if ((rc = tower_backward(T, W, D, s, 2, nullptr, BWD_GATE))) return rc;
-            TTAMM_HIP(hipEventRecord(ev[4], s));
-            TTAMM_HIP(hipStreamWaitEvent(aux, ev[4], 0));
-            if (fin_aux && (rc = finalize(aux))) return rc;
-            // on the aux stream: the grouping before it there already, so no join
-            if ((rc = table_updates(T, W, 2, D, mimic, sp, ad, df, A.timing_events, aux, aux))) return rc;
-            TTAMM_HIP(hipEventRecord(ev[5], aux));
-            if ((rc = tower_backward(T, W, D, s, 2, A.timing_events + 6, BWD_MLP))) return rc;
-            if ((rc = dense_update(T, W, ad, A.status, s))) return rc;
-            TTAMM_HIP(hipStreamWaitEvent(s, ev[5], 0));
-            return TTAMM_OK;
-        }
+        TTAMM_REQUIRE(!ws.ib_on || A.inbatch_dp, "sharded in-batch USER phase needs inbatch_dp");
+        if ((rc = launch_score_loss(bind_score(c), s))) return rc;
+        if (ws.cal_on && (rc = launch_cal_finish(bind_cal_grads(c), s))) return rc;
+        if ((rc = loss_finalize(c, s))) return rc;
         if (ph & TTAMM_PHASE_USER) {
-            if ((rc = tower_backward(T, W, D, s, 1))) return rc;
-            if ((rc = table_updates(T, W, 1, D, mimic, sp, ad, df, nullptr, s, aux))) return rc;
+            if ((rc = tower_backward(c.T, c.W, D, s, 1))) return rc;
+            if ((rc = table_updates(c, c.T, c.W, 1, pl, false, nullptr))) return rc;
         }
     }
-    // ---- grouped: both towers' backward and table updates ------------------------------------
-    if (ph & TTAMM_PHASE_TOWERS_BWD) {
-        static const bool rows_main = dev_env("TTAMM_ROWS_MAIN") != nullptr;
-        if (I.R > 0 && !ws.clip_on && !rows_main && aux != nullptr && aux != s && overlapped(T, 2, df, s, aux)) {
-            // as in one process: the touched-row updates on the aux stream beside the MLP backward,
-            // joined before this phase ends (the caller's all-reduce and DENSE follow)
-            hipEvent_t ev[kAuxEvents];
-            if ((rc = aux_events(ev, aux))) return rc;
-            if ((rc = tower_backward(T, W, D, s, 2, nullptr, BWD_GATE))) return rc;
-            TTAMM_HIP(hipEventRecord(ev[4], s));
-            TTAMM_HIP(hipStreamWaitEvent(aux, ev[4], 0));
-            if ((rc = table_updates(T, W, 2, D, mimic, sp, ad, df, A.timing_events, aux, aux))) return rc;
-            TTAMM_HIP(hipEventRecord(ev[5], aux));
-            if ((rc = tower_backward(T, W, D, s, 2, A.timing_events + 6, BWD_MLP))) return rc;
-            TTAMM_HIP(hipStreamWaitEvent(s, ev[5], 0));
-        } else {
-            if (I.R > 0) {
-                if ((rc = tower_backward(T, W, D, s, 2, A.timing_events + 6))) return rc;
-            } else {
-                if ((rc = tower_backward(T, W, D, s, 1))) return rc;
-                const size_t n = tower_grad_floats(A.item);
-                if (n) TTAMM_HIP(hipMemsetAsync(I.gw[0] ? I.gw[0] : I.ggw[0], 0, n * sizeof(float), s));
-            }
-            if (ws.clip_on) {  // the table updates wait for the global norm (TABLES, after the all-reduce)
-                if ((rc = clip_table_share(T, W, D, mimic, sp, ad, df, A, ws, s, aux))) return rc;
-            } else if ((rc = table_updates(T, W, 2, D, mimic, sp, ad, df, A.timing_events, s, aux))) {
-                return rc;
-            }
-        }
+    // ---- TOWERS_BWD (grouped): both towers' backward and table updates; with clipping the table
+    // updates wait for the global norm (TABLES, after the caller's all-reduce of this rank's share)
+    if ((ph & TTAMM_PHASE_TOWERS_BWD) && pl.rows) {
+        if ((rc = rows_beside_mlp(c, pl, false))) return rc;
+    } else if (ph & TTAMM_PHASE_TOWERS_BWD) {
+        if ((rc = tower_backward(c.T, c.W, D, s, I.R > 0 ? 2 : 1, I.R > 0 ? A.timing_events + 6 : nullptr))) return rc;
+        if (I.R == 0 && (rc = zero_item_grads(c, s))) return rc;
+        if ((rc = ws.clip_on ? clip_table_share(c, pl) : table_updates(c, c.T, c.W, 2, pl, false, A.timing_events)))
+            return rc;
     }
-    // ---- sharded clipping: the deferred table updates, scaled by clip_grad_norm_'s coefficient --
+    // ---- TABLES (clipping): the table updates, scaled by clip_grad_norm_'s coefficient
     if ((ph & TTAMM_PHASE_TABLES) && ws.clip_on) {
-        if ((rc = clip_coefficient_sharded(T, W, ad, A, ws, s))) return rc;
-        if ((rc = table_updates(T, W, 2, D, mimic, sp, ad, df, A.timing_events, s, aux, ws.clip_coef))) return rc;
+        if ((rc = clip_coefficient_sharded(c, s))) return rc;
+        if ((rc = table_updates(c, c.T, c.W, 2, pl, false, A.timing_events, ws.clip_coef))) return rc;
     }
-    // ---- item-side backward on the owner ------------------------------------------------------
+    // ---- ITEM_BWD: the item-side backward and table updates on the owner
     if (ph & TTAMM_PHASE_ITEM_BWD) {
-        const ttamm_tower* Ti[2] = {&A.item, nullptr};
-        TowerWs* Wi[2] = {&I, nullptr};
-        if (I.R > 0) {
-            if ((rc = tower_backward(Ti, Wi, D, s, 1, A.timing_events + 6))) return rc;
-        } else {
-            // no requests: this rank's item-tower gradient share is zero
-            const size_t n = tower_grad_floats(A.item);
-            if (n) TTAMM_HIP(hipMemsetAsync(I.gw[0] ? I.gw[0] : I.ggw[0], 0, n * sizeof(float), s));
-        }
-        if ((rc = table_updates(Ti, Wi, 1, D, mimic, sp, ad, df, A.timing_events, s, aux))) return rc;
+        if ((rc = I.R > 0 ? tower_backward(Ti, Wi, D, s, 1, A.timing_events + 6) : zero_item_grads(c, s))) return rc;
+        if ((rc = table_updates(c, Ti, Wi, 1, pl, false, A.timing_events))) return rc;
     }
-    if (ph & TTAMM_PHASE_DENSE)
-        if ((rc = dense_update(T, W, ad, A.status, s, ws.clip_on ? ws.clip_coef : nullptr))) return rc;
+    if (ph & TTAMM_PHASE_DENSE) return dense_update(c.T, c.W, c.ad, A.status, s, ws.clip_on ? ws.clip_coef : nullptr);
     return TTAMM_OK;
 }
 
@@ -2128,51 +2135,38 @@ size_t train_step_workspace_size(const ttamm_step_args& A) {
 int exchange_compact_supported(const ttamm_step_args& A) {
     if (!A.mimic_enabled || A.item.fusion != TTAMM_FUSION_GATED) return 0;
     const int D = out_dim(A.user);
-    // gate_group's choice as the step makes it: a gated tower has gate16 weight images exactly when
-    // plan() gives it some (a stand-in pointer here; gate_group only tests it)
-    static uint16_t stand_in;
-    TowerWs u, it;
-    const ttamm_tower* T2[2] = {&A.user, &A.item};
-    TowerWs* W2[2] = {&u, &it};
-    for (int k = 0; k < 2; ++k) {
-        W2[k]->R = 1;
-        const ttamm_tower& t = *T2[k];
-        if (t.fusion == TTAMM_FUSION_GATED && gate16_supported(D, t.gate[0].out_features, t.matmul_bf16 ? 1 : 3))
-            W2[k]->gw16 = &stand_in;
-    }
-    GateArgs ga;
-    const ttamm_tower* Ti[2] = {&A.item, nullptr};
-    TowerWs* Wi[2] = {&it, nullptr};
-    if (!gate_group(Ti, Wi, 1, D, true, ga)) return 0;
-    return gate_group(T2, W2, 2, D, true, ga) ? 1 : 0;
+    // the gate's choice as the step makes it, for the item tower alone (ITEM_FWD / ITEM_BWD) and for
+    // both towers grouped: a gated tower has gate16 weight images exactly when plan() gives it some
+    const ttamm_tower* T[2] = {&A.item, &A.user};
+    bool has16[2];
+    for (int k = 0; k < 2; ++k)
+        has16[k] = T[k]->fusion == TTAMM_FUSION_GATED &&
+                   gate16_supported(D, T[k]->gate[0].out_features, T[k]->matmul_bf16 ? 1 : 3);
+    int hg, planes;
+    return gate_choice(T, has16, 1, D, hg, planes) && gate_choice(T, has16, 2, D, hg, planes) ? 1 : 0;
 }
 
 int64_t dense_grad_floats(const ttamm_step_args& A) {
     return (int64_t)(tower_grad_floats(A.user) + tower_grad_floats(A.item));
 }
 
-int train_step(const ttamm_step_args& A, hipStream_t s) { return run_step(A, s); }
+int train_step(const ttamm_step_args& A, hipStream_t s) {
+    Step c(A);
+    int rc;
+    if ((rc = bind_rows(c))) return rc;
+    const StreamPlan pl = stream_plan(A, c.df, c.ws.clip_on, s);
+    if (pl.rc) return pl.rc;
+    return sharded(A) ? run_phases(c, pl) : run_single(c, pl);
+}
 
 int flush_tables(const ttamm_step_args& A, hipStream_t s) {
     Deferred df;
     int rc;
     if ((rc = deferred_of(A, df))) return rc;
     if (!df.on) return TTAMM_OK;
-    // With an aux stream the flush runs there, behind the last step's table updates and slice (which
-    // it must follow) and beside the main stream's tail of that step (weight gradients, their reduce,
-    // the dense update: no table rows), and the main stream waits for it: its next reader of the
-    // tables is the next step's gather (round 6: the flush overlaps ~0.15 ms of that tail)
-    hipStream_t aux = static_cast<hipStream_t>(A.aux_stream);
-    const hipStream_t run = (aux != nullptr && aux != s) ? aux : s;
-    ReplayArgs ra;
-    std::memset(&ra, 0, sizeof(ra));
-    ra.hist = df.hist;
-    ra.cap = df.cap;
-    ra.decoupled = df.decoupled;
-    ra.sgd = df.sgd;
-    ra.fast_g0 = df.fast;
-    ra.target = df.step;
-    ra.stamp = 1;
+    const StreamPlan pl = stream_plan(A, df, A.hp.grad_clip_norm > 0.0, s);
+    if (pl.rc) return pl.rc;
+    ReplayArgs ra = replay_header(df, df.step, 1);
     for (const ttamm_tower* t : {&A.user, &A.item}) {
         const ttamm_table* tabs[2];
         const int n = dense_tables(*t, A.mimic_enabled != 0, tabs);
@@ -2183,14 +2177,20 @@ int flush_tables(const ttamm_step_args& A, hipStream_t s) {
             ra.seg[ra.count++] = g;
         }
     }
-    if ((rc = launch_replay(ra, run))) return rc;
-    if (run != s) {
-        hipEvent_t e;
-        TTAMM_HIP(create_sync_event(&e));
-        TTAMM_HIP(hipEventRecord(e, run));
-        TTAMM_HIP(hipStreamWaitEvent(s, e, 0));
-        TTAMM_HIP(hipEventDestroy(e));
+    if (!pl.aux) return launch_replay(ra, s);
+    // With an aux stream the flush runs there (StreamPlan (c)): behind whatever wrote the tables —
+    // the last step's row updates and slice on that stream already (tables_on_aux: the flush then
+    // runs beside the main stream's tail of that step, the weight gradients, their reduce and the
+    // dense update, which touch no table row; ~0.15 ms at C2), anything else on `s`, which the aux
+    // stream waits for — and the main stream waits for it: the caller may read the tables, and the
+    // next step gather them, without a host sync in between.
+    if (!pl.tables_on_aux) {
+        TTAMM_HIP(hipEventRecord(pl.ev[EV_TO_AUX], s));
+        TTAMM_HIP(hipStreamWaitEvent(pl.aux, pl.ev[EV_TO_AUX], 0));
     }
+    if ((rc = launch_replay(ra, pl.aux))) return rc;
+    TTAMM_HIP(hipEventRecord(pl.ev[EV_FROM_AUX], pl.aux));
+    TTAMM_HIP(hipStreamWaitEvent(s, pl.ev[EV_FROM_AUX], 0));
     return TTAMM_OK;
 }
 
@@ -2313,18 +2313,7 @@ void plan_tower_train(Arena& ar, const ttamm_tower& T, int64_t n, TowerWs& w) {
     int rps[kWgradClasses] = {512, 512, 512, 512};
     if (ns) wgrad_rows_per_split(shapes, ns, rps);
     for (int c = 0; c < kWgradClasses; ++c) w.wgrad_rps[c] = rps[c];
-    if (T.fusion != TTAMM_FUSION_IDENTITY) {
-        for (int l = 0; l < T.n_linear; ++l) {
-            const ttamm_linear& L = T.linear[l];
-            w.slab[l] = ar.take<float>(wgrad_slab_floats((int)n, L.out_features, L.in_features,
-                                                         w.wgrad_rps[wgrad_class(L.out_features)]));
-        }
-        for (int q = 0; q < fusion_linears(T); ++q) {
-            const ttamm_linear& L = T.gate[q];
-            w.slab[TTAMM_MAX_LINEAR + q] = ar.take<float>(
-                wgrad_slab_floats((int)n, L.out_features, L.in_features, w.wgrad_rps[wgrad_class(L.out_features)]));
-        }
-    }
+    plan_slabs(ar, T, n, w);
     if (needs_wpad(T)) w.wpad = ar.take<float>((size_t)T.linear[0].out_features * round4(T.linear[0].in_features));
     if (T.id.max_norm > 0.0) w.renorm_mark = ar.take<int32_t>(T.id.rows);
 }
