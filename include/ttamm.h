@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define TTAMM_ABI_VERSION 25
+#define TTAMM_ABI_VERSION 26
 
 #define TTAMM_OK 0
 #define TTAMM_E_INVALID 1 /* bad shape / config / dtype  -> ValueError   */
@@ -409,6 +409,32 @@ int ttamm_train_step(const ttamm_step_args* args, void* stream);
  * mimic on and the item tower's gate on the fused kernels (gate.hip / gate16.hip), alone and
  * grouped with the user tower; 0 otherwise (the 2*dim-wide rows).  Host-only, no device work. */
 int ttamm_exchange_compact_supported(const ttamm_step_args* args);
+
+/* Replaces one iteration of `_compute_loss` (training.py:854-910): negative sampling, both tower
+ * forwards in eval mode (dropout off; nn.Embedding's max_norm renorm kept, the positives and the
+ * negatives as the item table's two lookups, :875 and :887), mimic augmentation, dot-product
+ * scores and the BCEWithLogits mean over cat([pos_logits, neg_logits]) (:898-907).  Forward only:
+ * no parameter, gradient or optimizer state is written (apart from that renorm), and the
+ * optimizer-state pointers of the descriptors may be NULL.  The tables are read as they are, so
+ * deferred tables (ttamm_table.last_step) must have been flushed first (ttamm_flush_tables).
+ *   read:     user, item, mimic_enabled, b.{users, pos_items, neg_items, batch, num_neg,
+ *             sample_negatives, pos_offsets, pos_values, seed, counter}, row_base and
+ *             num_items_global (the sampler's keying and range, as in the training step),
+ *             loss_out, loss_accum (may be NULL), status, workspace, workspace_bytes.
+ *             b.sample_negatives != 0 draws the negatives into b.neg_items (NULL: kept in the
+ *             workspace only); ids outside their table set TTAMM_STATUS_INDEX_OUT_OF_RANGE and
+ *             read row 0.
+ *   ignored:  hp, b.*_keep_mask, aux_stream, timing_events, steps_applied, the tables' last_step
+ *             and touched, and every other field.
+ *   rejected: phase != TTAMM_PHASE_ALL, in_batch != 0, b.num_neg outside [1, 64], an empty batch,
+ *             NULL loss_out / status / workspace, a workspace smaller than
+ *             ttamm_eval_loss_workspace_size (TTAMM_E_INVALID).
+ * loss_out[0] = loss_out[1] = the batch's BCE, loss_out[2..4] = 0; loss_accum += (bce * batch,
+ * batch) — `running_loss` / `total_samples` of :909-910.  The sum runs in a fixed order (no float
+ * atomics): the same inputs give the same bits.  With a non-zero status word the loss outputs are
+ * left as they were.  logits_out, when given, receives every logit in the order of :898. */
+size_t ttamm_eval_loss_workspace_size(const ttamm_step_args* args);
+int ttamm_eval_loss(const ttamm_step_args* args, float* logits_out /* [batch*(1+num_neg)] or NULL */, void* stream);
 
 /* Size (floats) of the replicated-weight gradient arena of a sharded step: both towers'
  * feature-encoder and gate weight+bias gradients, contiguous (the all-reduce buffer). */

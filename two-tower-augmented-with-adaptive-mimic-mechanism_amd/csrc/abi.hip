@@ -24,6 +24,8 @@ int train_step(const ttamm_step_args& A, hipStream_t s);
 int64_t dense_grad_floats(const ttamm_step_args& A);
 int exchange_compact_supported(const ttamm_step_args& A);
 int flush_tables(const ttamm_step_args& A, hipStream_t s);
+size_t eval_loss_workspace_size(const ttamm_step_args& A);
+int eval_loss(const ttamm_step_args& A, float* logits_out, hipStream_t s);
 size_t tower_forward_workspace_size(const ttamm_tower& T, int64_t n);
 int tower_forward_eval(const ttamm_tower& T, const int64_t* idx, const int64_t* fidx, int64_t n, int augment,
                        float* out, void* ws, size_t ws_bytes, hipStream_t s);
@@ -159,6 +161,17 @@ TTAMM_API int ttamm_train_step(const ttamm_step_args* args, void* stream) {
     if (!args) return fail(TTAMM_E_INVALID, "null step args");
     g_last_error.clear();
     return train_step(*args, (hipStream_t)stream);
+}
+
+TTAMM_API size_t ttamm_eval_loss_workspace_size(const ttamm_step_args* args) {
+    if (!args) return 0;
+    return eval_loss_workspace_size(*args);
+}
+
+TTAMM_API int ttamm_eval_loss(const ttamm_step_args* args, float* logits_out, void* stream) {
+    if (!args) return fail(TTAMM_E_INVALID, "null step args");
+    g_last_error.clear();
+    return eval_loss(*args, logits_out, (hipStream_t)stream);
 }
 
 TTAMM_API int ttamm_gather_rows(const float* table, int64_t table_rows, int32_t dim, const int64_t* idx, int64_t n,

@@ -346,6 +346,24 @@ struct ScoreArgs {
 };
 int score_blocks(int64_t B, int D);  // [blocks, 3] partials of launch_score_loss
 int launch_score_loss(const ScoreArgs& a, hipStream_t s);
+// Forward-only scorer of a validation batch (ttamm_eval_loss): logits and BCE terms, no gradients
+struct EvalScoreArgs {
+    int64_t B;
+    int N;
+    int D;
+    const float* user_aug;  // [B, D]
+    const float* item_aug;  // [B(1+N), ld_item], rows [positives; negatives b-major]
+    int64_t ld_item;
+    float* partials;        // [blocks]: per-block sums of the BCE terms
+    int blocks;             // score_blocks(B, D)
+    float* logits;          // [B(1+N)] = cat([pos_logits, neg_logits.reshape(-1)]) (training.py:898), or null
+};
+int score_eval_check(int N, int D);  // the scorer's limits: 1 <= N <= 64, D <= 512
+int launch_score_eval(const EvalScoreArgs& a, hipStream_t s);
+// bce = sum(partials) / count in a fixed order; loss_out = [bce, bce, 0, 0, 0], loss_accum += (bce B, B);
+// writes nothing when *status != 0
+int launch_eval_loss_finalize(const float* partials, int blocks, int64_t count, int64_t B, float* loss_out,
+                              double* loss_accum, const uint32_t* status, hipStream_t s);
 // bce = (sum of the score partials + sum of ib_partials) / bce_count
 int launch_loss_finalize(const float* partials, int blocks, const float* ib_partials, int ib_blocks, int64_t bce_count,
                          int64_t B, int64_t Bg, int D, float lambda_u, float lambda_i, int mimic, const float* cal,

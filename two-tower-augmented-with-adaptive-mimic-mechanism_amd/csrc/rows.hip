@@ -534,6 +534,163 @@ __global__ __launch_bounds__(64 * kScoreWaves) void score_loss_v_kernel(ScoreArg
     }
 }
 
+// Forward-only scorer of a validation batch (`_compute_loss`, training.py:881-907): the logits
+// s+ = <u_b, p_b>, s-_j = <u_b, n_bj> of the augmented rows and their BCE terms, nothing else —
+// no gradient row is written.  score_loss_kernel's mapping (one wave per interaction, NCH chunks
+// per lane, the negatives' rows requested in groups of kScoreNG before the first reduction) and
+// its sums, so a logit has the bits the training scorer gives the same rows.
+template <int NCH>
+__global__ __launch_bounds__(64 * kScoreWaves) void score_eval_kernel(EvalScoreArgs A) {
+    __shared__ float red[kScoreWaves];
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const int64_t b = (int64_t)blockIdx.x * kScoreWaves + w;
+    const int D = A.D, N = A.N;
+    const int64_t B = A.B, ldi = A.ld_item;
+    float bce = 0.f;
+    if (b < B) {
+        bool ok[NCH];
+        float u[NCH], p[NCH];
+#pragma unroll
+        for (int c = 0; c < NCH; ++c) {
+            const int d = c * 64 + lane;
+            ok[c] = d < D;
+            u[c] = ok[c] ? A.user_aug[b * D + d] : 0.f;
+            p[c] = ok[c] ? A.item_aug[b * ldi + d] : 0.f;
+        }
+        float dot = 0.f;
+#pragma unroll
+        for (int c = 0; c < NCH; ++c)
+            if (ok[c]) dot += u[c] * p[c];
+        const float sp = wave_sum(dot);
+        bce += bce_logit(sp, 1.0f);
+        if (A.logits && lane == 0) A.logits[b] = sp;
+        for (int j0 = 0; j0 < N; j0 += kScoreNG) {
+            const int ng = N - j0 < kScoreNG ? N - j0 : kScoreNG;
+            float nv[kScoreNG][NCH];
+#pragma unroll
+            for (int jj = 0; jj < kScoreNG; ++jj) {
+                const int64_t q = jj < ng ? B + b * N + j0 + jj : 0;
+#pragma unroll
+                for (int c = 0; c < NCH; ++c) nv[jj][c] = (jj < ng && ok[c]) ? A.item_aug[q * ldi + c * 64 + lane] : 0.f;
+            }
+            float sn[kScoreNG];
+#pragma unroll
+            for (int jj = 0; jj < kScoreNG; ++jj) {
+                float dn = 0.f;
+#pragma unroll
+                for (int c = 0; c < NCH; ++c)
+                    if (ok[c]) dn += u[c] * nv[jj][c];
+                sn[jj] = jj < ng ? wave_sum(dn) : 0.f;
+            }
+#pragma unroll
+            for (int jj = 0; jj < kScoreNG; ++jj) {
+                if (jj >= ng) continue;
+                bce += bce_logit(sn[jj], 0.0f);
+                if (A.logits && lane == 0) A.logits[B + b * N + j0 + jj] = sn[jj];
+            }
+        }
+    }
+    if (lane == 0) red[w] = bce;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        float s = 0.f;
+        for (int i = 0; i < kScoreWaves; ++i) s += red[i];
+        A.partials[blockIdx.x] = s;
+    }
+}
+
+// The same with score_loss_v_kernel's mapping: G lanes per interaction, NV float4 columns per
+// lane (D = 4 G NV), 16-byte loads, each dot product reduced over log2 G lanes.
+template <int G, int NV>
+__global__ __launch_bounds__(64 * kScoreWaves) void score_eval_v_kernel(EvalScoreArgs A) {
+    constexpr int NG = NV <= 3 ? 8 : 4;  // negatives in flight per group
+    __shared__ float red[kScoreWaves];
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, s = lane % G;
+    const int64_t b = ((int64_t)blockIdx.x * kScoreWaves + w) * (64 / G) + lane / G;
+    constexpr int D = 4 * G * NV;
+    const int N = A.N;
+    const int64_t B = A.B, ldi = A.ld_item;
+    float bce = 0.f;
+    if (b < B) {
+        const float4 z4 = make_float4(0.f, 0.f, 0.f, 0.f);
+        float4 u[NV], p[NV];
+#pragma unroll
+        for (int i = 0; i < NV; ++i) {
+            const int c = 4 * (s + G * i);
+            u[i] = ld4(A.user_aug + b * D + c);
+            p[i] = ld4(A.item_aug + b * ldi + c);
+        }
+        float dot = 0.f;
+#pragma unroll
+        for (int i = 0; i < NV; ++i) dot += dot4(u[i], p[i]);
+        const float sp = group_sum(dot, G);
+        bce += bce_logit(sp, 1.0f);
+        if (A.logits && s == 0) A.logits[b] = sp;
+        for (int j0 = 0; j0 < N; j0 += NG) {
+            const int ng = N - j0 < NG ? N - j0 : NG;
+            float4 nv[NG][NV];
+#pragma unroll
+            for (int jj = 0; jj < NG; ++jj) {
+                const int64_t q = jj < ng ? B + b * N + j0 + jj : 0;
+#pragma unroll
+                for (int i = 0; i < NV; ++i) nv[jj][i] = jj < ng ? ld4(A.item_aug + q * ldi + 4 * (s + G * i)) : z4;
+            }
+            float sn[NG];
+#pragma unroll
+            for (int jj = 0; jj < NG; ++jj) {
+                float dn = 0.f;
+#pragma unroll
+                for (int i = 0; i < NV; ++i) dn += dot4(u[i], nv[jj][i]);
+                sn[jj] = group_sum(dn, G);
+            }
+#pragma unroll
+            for (int jj = 0; jj < NG; ++jj) {
+                if (jj >= ng) continue;
+                bce += bce_logit(sn[jj], 0.0f);
+                if (A.logits && s == 0) A.logits[B + b * N + j0 + jj] = sn[jj];
+            }
+        }
+    }
+    // every lane of a group holds the group's BCE terms: count them once
+    bce = wave_sum(s == 0 ? bce : 0.f);
+    if (lane == 0) red[w] = bce;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        float t = 0.f;
+        for (int i = 0; i < kScoreWaves; ++i) t += red[i];
+        A.partials[blockIdx.x] = t;
+    }
+}
+
+// Fixed-order sum of score_eval's per-block partials (no float atomics: the same inputs give the
+// same bits); loss_out = [bce, bce, 0, 0, 0], loss_accum += (bce B, B) as `_compute_loss`
+// accumulates (training.py:907-910).  A non-zero status word: nothing is written.
+__global__ void eval_loss_finalize_kernel(const float* __restrict__ partials, int blocks, int64_t count, int64_t B,
+                                          float* __restrict__ loss_out, double* __restrict__ loss_accum,
+                                          const uint32_t* __restrict__ status) {
+    __shared__ float red[256];
+    float s = 0.f;
+    for (int i = threadIdx.x; i < blocks; i += blockDim.x) s += partials[i];
+    red[threadIdx.x] = s;
+    __syncthreads();
+    for (int o = blockDim.x / 2; o > 0; o >>= 1) {
+        if (threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0 && *status == 0u) {
+        const float bce = red[0] / (float)count;
+        loss_out[0] = bce;
+        loss_out[1] = bce;
+        loss_out[2] = 0.f;
+        loss_out[3] = 0.f;
+        loss_out[4] = 0.f;
+        if (loss_accum) {
+            loss_accum[0] += (double)bce * (double)B;
+            loss_accum[1] += (double)B;
+        }
+    }
+}
+
 // Deterministic final reduction of the per-block partials; total loss as in training.py:798-803.
 __global__ void loss_finalize_kernel(const float* __restrict__ partials, int blocks, const float* __restrict__ ib_partials,
                                      int ib_blocks, int64_t bce_count, int64_t B, int64_t Bg, int D,
@@ -844,6 +1001,55 @@ int launch_score_loss(const ScoreArgs& a, hipStream_t s) {
         case 5: case 6: hipLaunchKernelGGL(score_loss_kernel<6>, g, t, 0, s, a); break;
         default: hipLaunchKernelGGL(score_loss_kernel<8>, g, t, 0, s, a); break;
     }
+    TTAMM_LAUNCH_CHECK();
+    return TTAMM_OK;
+}
+
+int score_eval_check(int N, int D) {
+    TTAMM_REQUIRE(D <= 64 * kMaxDChunks, "score: embedding dim too large (max 512)");
+    TTAMM_REQUIRE(N >= 1 && N <= kMaxNeg, "score: b.num_neg (negatives_per_positive) must be in [1, 64]");
+    return TTAMM_OK;
+}
+
+int launch_score_eval(const EvalScoreArgs& a, hipStream_t s) {
+    int rc;
+    if ((rc = score_eval_check(a.N, a.D))) return rc;
+    if (a.B <= 0) return TTAMM_OK;
+    TTAMM_REQUIRE(a.user_aug && a.item_aug && a.partials && a.ld_item >= a.D, "score: bad arguments");
+    TTAMM_REQUIRE(a.blocks == score_blocks(a.B, a.D), "score: partials sized for another batch");
+    const dim3 g(a.blocks), t(64 * kScoreWaves);
+    const bool al = ((uintptr_t)a.user_aug | (uintptr_t)a.item_aug) % 16 == 0 && a.ld_item % 4 == 0;
+    if (al && score_group(a.D)) {
+        switch (a.D) {
+            case 32: hipLaunchKernelGGL((score_eval_v_kernel<8, 1>), g, t, 0, s, a); break;
+            case 64: hipLaunchKernelGGL((score_eval_v_kernel<8, 2>), g, t, 0, s, a); break;
+            case 96: hipLaunchKernelGGL((score_eval_v_kernel<8, 3>), g, t, 0, s, a); break;
+            case 128: hipLaunchKernelGGL((score_eval_v_kernel<8, 4>), g, t, 0, s, a); break;
+            case 192: hipLaunchKernelGGL((score_eval_v_kernel<16, 3>), g, t, 0, s, a); break;
+            case 256: hipLaunchKernelGGL((score_eval_v_kernel<16, 4>), g, t, 0, s, a); break;
+            case 384: hipLaunchKernelGGL((score_eval_v_kernel<16, 6>), g, t, 0, s, a); break;
+            default: hipLaunchKernelGGL((score_eval_v_kernel<16, 8>), g, t, 0, s, a); break;
+        }
+        TTAMM_LAUNCH_CHECK();
+        return TTAMM_OK;
+    }
+    switch ((a.D + 63) / 64) {
+        case 1: hipLaunchKernelGGL(score_eval_kernel<1>, g, t, 0, s, a); break;
+        case 2: hipLaunchKernelGGL(score_eval_kernel<2>, g, t, 0, s, a); break;
+        case 3: hipLaunchKernelGGL(score_eval_kernel<3>, g, t, 0, s, a); break;
+        case 4: hipLaunchKernelGGL(score_eval_kernel<4>, g, t, 0, s, a); break;
+        case 5: case 6: hipLaunchKernelGGL(score_eval_kernel<6>, g, t, 0, s, a); break;
+        default: hipLaunchKernelGGL(score_eval_kernel<8>, g, t, 0, s, a); break;
+    }
+    TTAMM_LAUNCH_CHECK();
+    return TTAMM_OK;
+}
+
+int launch_eval_loss_finalize(const float* partials, int blocks, int64_t count, int64_t B, float* loss_out,
+                              double* loss_accum, const uint32_t* status, hipStream_t s) {
+    TTAMM_REQUIRE(partials && blocks > 0 && count > 0 && loss_out && status, "eval loss finalize: bad arguments");
+    hipLaunchKernelGGL(eval_loss_finalize_kernel, dim3(1), dim3(256), 0, s, partials, blocks, count, B, loss_out,
+                       loss_accum, status);
     TTAMM_LAUNCH_CHECK();
     return TTAMM_OK;
 }

@@ -2271,6 +2271,159 @@ int tower_forward_eval(const ttamm_tower& T, const int64_t* idx, const int64_t* 
     return TTAMM_OK;
 }
 
+// ---- validation loss: one forward-only batch of `_compute_loss` (training.py:854-910) --------
+//   sample negatives (b.sample_negatives)          samplers.py:11-85, the step's Philox keying
+//   stage + range-check users, [pos; neg]          bad ids set the status bit and read row 0
+//   both towers, grouped, eval mode                dropout off, max_norm renorm kept
+//                                                  (positives and negatives as two lookups)
+//   scores + BCE terms, fixed-order mean           training.py:881-907
+// Everything runs on the caller's stream.  The tables are read as they are: deferred AdamW
+// tables (ttamm_table.last_step) must have been flushed (ttamm_flush_tables;
+// FusedTrainStep.finish() does it).  No parameter or optimizer state is written, apart from the
+// max_norm renorm of the looked-up ID rows.
+namespace {
+struct EvalWs {
+    TowerWs user, item;
+    float* partials = nullptr;
+    int blocks = 0;
+};
+
+// Forward buffers for B and B(1+N) rows, the staged ids, the weight pads / images the forward
+// forms and the score partials: no backward buffer, gradient slab or coalesce scratch.
+void plan_eval(Arena& ar, const ttamm_step_args& A, EvalWs& ws) {
+    const int64_t B = A.b.batch;
+    const int N = A.b.num_neg;
+    const int D = out_dim(A.user);
+    const bool mimic = A.mimic_enabled != 0;
+    auto tower = [&](const ttamm_tower& T, TowerWs& w, int64_t R) {
+        w.R = R;
+        w.idx_own = ar.take<int64_t>(R);
+        for (int l = 0; l + 1 < T.n_linear; ++l) w.hid[l] = ar.take<float>((size_t)R * T.linear[l].out_features);
+        if (uses_ef(T)) {
+            w.ef = ar.take<float>((size_t)R * efw(T));
+        } else {
+            w.e = ar.take<float>((size_t)R * D);
+            if (T.fusion == TTAMM_FUSION_SUM) w.f = ar.take<float>((size_t)R * D);
+        }
+        if (T.fusion == TTAMM_FUSION_GATED) {
+            const int Hg = T.gate[0].out_features;
+            w.z = ar.take<float>((size_t)R * Hg);
+            w.g = ar.take<float>((size_t)R * D);
+            const int np = T.matmul_bf16 ? 1 : 3;
+            if (gate16_supported(D, Hg, np)) w.gw16 = ar.take<uint16_t>((size_t)gate16_image_elems(D, Hg, np));
+        }
+        w.t = ar.take<float>((size_t)R * D);
+        w.a = mimic ? ar.take<float>((size_t)R * D) : nullptr;
+        w.t_ld = D;
+        w.aug = ar.take<float>((size_t)R * D);
+        if (needs_wpad(T)) w.wpad = ar.take<float>((size_t)T.linear[0].out_features * round4(T.linear[0].in_features));
+        if (uses_w16(T)) w.w16 = ar.take<uint16_t>((size_t)T.linear[0].out_features * round8(T.linear[0].in_features));
+        if (T.id.max_norm > 0.0) w.renorm_mark = ar.take<int32_t>(T.id.rows);
+    };
+    ws.user.role = ROLE_USER;
+    ws.item.role = ROLE_ITEM;
+    tower(A.user, ws.user, B);
+    tower(A.item, ws.item, B * (1 + (int64_t)N));
+    ws.blocks = score_blocks(B, D);
+    ws.partials = ar.take<float>((size_t)ws.blocks);
+}
+
+int validate_eval(const ttamm_step_args& A) {
+    const int D = out_dim(A.user);
+    int rc;
+    if ((rc = validate_tower(A.user, "user_encoder", D, false))) return rc;
+    if ((rc = validate_tower(A.item, "item_encoder", D, false))) return rc;
+    TTAMM_REQUIRE(out_dim(A.item) == D, "User and item encoders must produce embeddings with the same dimension.");
+    TTAMM_REQUIRE(A.user.matmul_bf16 == A.item.matmul_bf16, "user and item towers must share one matmul precision");
+    TTAMM_REQUIRE(A.phase == TTAMM_PHASE_ALL, "eval loss: phase must be 0, the whole batch in one call (no sharded validation pass)");
+    TTAMM_REQUIRE(A.in_batch == 0, "eval loss: in_batch must be 0 (_compute_loss scores sampled negatives only)");
+    if ((rc = score_eval_check(A.b.num_neg, D))) return rc;
+    TTAMM_REQUIRE(A.b.batch > 0, "empty batch");
+    if (A.mimic_enabled) {
+        TTAMM_REQUIRE(A.user.mimic.weight && A.item.mimic.weight, "mimic tables missing");
+        TTAMM_REQUIRE(A.user.mimic.dim == D && A.item.mimic.dim == D &&
+                          A.user.mimic.rows == A.user.id.rows && A.item.mimic.rows == A.item.id.rows,
+                      "Adaptive mimic requires user and item embedding dimensions to match.");
+    }
+    return TTAMM_OK;
+}
+}  // namespace
+
+size_t eval_loss_workspace_size(const ttamm_step_args& A) {
+    Arena ar{nullptr, 0, 0, true};
+    EvalWs ws;
+    plan_eval(ar, A, ws);
+    return ar.off + 256;
+}
+
+int eval_loss(const ttamm_step_args& A, float* logits_out, hipStream_t s) {
+    int rc;
+    if ((rc = validate_eval(A))) return rc;
+    TTAMM_REQUIRE(A.loss_out && A.status && A.workspace, "eval loss: loss_out, status and workspace are required");
+    TTAMM_REQUIRE(A.b.users && A.b.pos_items, "eval loss: b.users / b.pos_items missing");
+    const int D = out_dim(A.user);
+    const bool mimic = A.mimic_enabled != 0;
+    const int64_t B = A.b.batch;
+    const int N = A.b.num_neg;
+    EvalWs ws;
+    Arena ar{static_cast<char*>(A.workspace), A.workspace_bytes, 0, false};
+    plan_eval(ar, A, ws);
+    TTAMM_REQUIRE(ar.ok(), "workspace too small for this eval loss batch");
+    TowerWs &U = ws.user, &I = ws.item;
+    int64_t* neg_rows = I.idx_own + B;
+    const int64_t* neg_src = A.b.neg_items;
+    if (A.b.sample_negatives) {  // the training step's draws for (seed, counter, row_base)
+        const int64_t num_items = A.num_items_global > 0 ? A.num_items_global : A.item.id.rows;
+        int64_t* dst = A.b.neg_items ? A.b.neg_items : neg_rows;
+        if ((rc = launch_sample_negatives(A.b.users, B, N, num_items, A.b.pos_offsets, A.b.pos_values, A.user.id.rows,
+                                          A.b.seed, A.b.counter, A.row_base * N, dst, nullptr, A.status, s)))
+            return rc;
+        neg_src = dst;
+    }
+    TTAMM_REQUIRE(neg_src != nullptr, "negatives must be given when sample_negatives == 0");
+    {
+        StageArgs st;
+        std::memset(&st, 0, sizeof(st));
+        st.status = A.status;
+        st.seg[st.count++] = StageSeg{A.b.users, U.idx_own, B, A.user.id.rows};
+        st.seg[st.count++] = StageSeg{A.b.pos_items, I.idx_own, B, A.item.id.rows};
+        st.seg[st.count++] = StageSeg{neg_src, neg_rows, B * N, A.item.id.rows};
+        if ((rc = launch_stage_rows(st, s))) return rc;
+    }
+    U.idx = U.fidx = U.idx_own;
+    I.idx = I.fidx = I.idx_own;
+    // nn.Embedding(max_norm) renorms in eval mode too: the claim marks are cleared per call, the
+    // users are one lookup, the positives and the negatives the item table's two (training.py:875,887)
+    for (TowerWs* w : {&U, &I})
+        if (w->renorm_mark) {
+            const ttamm_tower& T = w == &U ? A.user : A.item;
+            TTAMM_HIP(hipMemsetAsync(w->renorm_mark, 0, (size_t)T.id.rows * sizeof(int32_t), s));
+            w->renorm_tag = 1;
+        }
+    I.renorm_split = B;
+    // eval mode: dropout off (a copy of each tower; the caller's descriptors are not changed)
+    ttamm_tower tu = A.user, ti = A.item;
+    tu.dropout = ti.dropout = 0.f;
+    ttamm_batch bt;
+    std::memset(&bt, 0, sizeof(bt));
+    const ttamm_tower* TT[2] = {&tu, &ti};
+    TowerWs* WW[2] = {&U, &I};
+    if ((rc = tower_forward(TT, WW, bt, D, mimic, s, 2))) return rc;
+    EvalScoreArgs sa;
+    std::memset(&sa, 0, sizeof(sa));
+    sa.B = B;
+    sa.N = N;
+    sa.D = D;
+    sa.user_aug = U.aug;
+    sa.item_aug = I.aug;
+    sa.ld_item = D;
+    sa.partials = ws.partials;
+    sa.blocks = ws.blocks;
+    sa.logits = logits_out;
+    if ((rc = launch_score_eval(sa, s))) return rc;
+    return launch_eval_loss_finalize(ws.partials, ws.blocks, B * (1 + (int64_t)N), B, A.loss_out, A.loss_accum, A.status, s);
+}
+
 
 // ---- training-mode tower forward / backward (module-level autograd) ------------------------
 // TowerEncoder.forward under autograd (encoders.py:221-255) in two calls: the forward keeps its

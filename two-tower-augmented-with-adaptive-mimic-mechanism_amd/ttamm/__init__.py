@@ -17,7 +17,14 @@ from .encoders import (
 from .inbatch import inbatch_bce
 from .retrieval import encode_item_embeddings, evaluate_model, prepare_faiss_resources
 from .samplers import PositivesCSR, sample_negative_items
-from .training import DotProductSimilarity, FusedTrainStep, _collect_parameter_groups, train_one_epoch
+from .training import (
+    DotProductSimilarity,
+    FusedEvalLoss,
+    FusedTrainStep,
+    _collect_parameter_groups,
+    compute_loss,
+    train_one_epoch,
+)
 from .two_tower import TwoTowerModel
 
 __all__ = [
@@ -27,6 +34,7 @@ __all__ = [
     "FeatureEncoderConfig",
     "FeatureEncoderWrapper",
     "FeatureFusionGate",
+    "FusedEvalLoss",
     "FusedTrainStep",
     "PositivesCSR",
     "TowerEncoder",
@@ -34,6 +42,7 @@ __all__ = [
     "build_feature_encoder",
     "build_id_embedding",
     "build_tower_encoder",
+    "compute_loss",
     "encode_item_embeddings",
     "evaluate_model",
     "inbatch_bce",

@@ -104,6 +104,18 @@ def _pad_features(features: torch.Tensor | None) -> torch.Tensor | None:
     return padded[:, :width]
 
 
+def _bf16_rows(feats: torch.Tensor) -> torch.Tensor:
+    """The feature rows rounded to bf16 (RNE), rows padded to a multiple of 8 elements
+    (ttamm_tower.features_bf16)."""
+    rows, width = feats.shape
+    ld = (width + 7) // 8 * 8
+    out = torch.empty((rows, ld), dtype=torch.bfloat16, device=feats.device)
+    lib = _lib.load()
+    _lib.check(lib.ttamm_to_bf16(feats.data_ptr(), rows, width, feats.stride(0), out.data_ptr(), ld,
+                                 _lib.stream_handle(feats.device)))
+    return out
+
+
 def _dense_params(opt: torch.optim.Optimizer) -> list[torch.Tensor]:
     return [p for g in opt.param_groups for p in g["params"]]
 
@@ -406,12 +418,7 @@ class FusedTrainStep:
 
     # ------------------------------------------------------------------------------------
     def _bf16_copy(self, feats: torch.Tensor) -> torch.Tensor:
-        rows, width = feats.shape
-        ld = (width + 7) // 8 * 8
-        out = torch.empty((rows, ld), dtype=torch.bfloat16, device=feats.device)
-        lib = _lib.load()
-        _lib.check(lib.ttamm_to_bf16(feats.data_ptr(), rows, width, feats.stride(0), out.data_ptr(), ld,
-                                     _lib.stream_handle(feats.device)))
+        out = _bf16_rows(feats)
         self._keep = getattr(self, "_keep", []) + [out]
         return out
 
@@ -697,6 +704,209 @@ def train_one_epoch(
         engine.step(users, pos, neg, keep_masks=masks)  # stream-ordered: inputs are recycled safely
         if step_losses is not None:
             step_losses.append(engine.loss_out.clone())
+        step += 1
+    if engine is None:
+        return 0.0
+    return engine.finish()
+
+
+# ---------------------------------------------------------------------------------------
+# validation loss: `_compute_loss` (training.py:836-914)
+# ---------------------------------------------------------------------------------------
+class FusedEvalLoss:
+    """Owns the native descriptor and workspace of the forward-only validation batch
+    (``ttamm_eval_loss``) for one model: eval-mode towers, mimic augment, dot-product scores and
+    the BCE mean, with the negatives drawn on the device.  No optimizer is involved and no
+    ``.grad`` is touched.  The tables are read as they are: after training with deferred AdamW,
+    call ``FusedTrainStep.finish()`` (it flushes them) before the first ``step`` here."""
+
+    def __init__(
+        self,
+        model: TwoTowerModel,
+        *,
+        negatives_per_positive: int,
+        positives: Mapping[int, set[int]] | PositivesCSR | None,
+        user_features: torch.Tensor | None,
+        item_features: torch.Tensor | None,
+        max_batch: int,
+        seed: int | None = None,
+        num_items: int | None = None,
+    ) -> None:
+        if negatives_per_positive <= 0:
+            raise ValueError("num_negatives must be greater than zero.")
+        self.model = model
+        self.num_neg = int(negatives_per_positive)
+        ue, ie = model.user_encoder, model.item_encoder
+        if not isinstance(ue, TowerEncoder) or not isinstance(ie, TowerEncoder):
+            raise NotImplementedError("ttamm: towers must be ttamm.encoders.TowerEncoder")
+        self.device = ue.embedding.weight.device
+        _lib.require_rocm(ue.embedding.weight, "FusedEvalLoss")
+        self.num_items = int(num_items) if num_items is not None else ie.num_embeddings
+        if self.num_items <= 1:
+            raise ValueError("num_items must be greater than one.")
+        mimic = getattr(model, "adaptive_mimic", None)
+        self.mimic = mimic
+        if mimic is not None and (ue.output_dim != ie.output_dim):
+            raise ValueError("Adaptive mimic requires user and item embedding dimensions to match.")
+        self.features = {"user": _pad_features(user_features), "item": _pad_features(item_features)}
+        self._keep: list[torch.Tensor] = []
+        args = _lib.StepArgs()
+        tables = {}
+        if mimic is not None:
+            tables = {"user": mimic.user_augmented.weight, "item": mimic.item_augmented.weight}
+        for name, tower in (("user", ue), ("item", ie)):
+            feats = self.features[name] if tower.fusion != "identity" else None
+            # no feature rows: the reference's tower falls back to the ID embedding (encoders.py:228-231)
+            desc = describe_tower(tower if feats is not None else _IdentityView(tower), features=feats,
+                                  mimic_table=tables.get(name), state=None)
+            if feats is not None and getattr(tower, "matmul_dtype", "fp32") == "bf16":
+                f16 = _bf16_rows(feats)  # the first layer streams bf16 operands, as in the training step
+                self._keep.append(f16)
+                desc.features_bf16 = f16.data_ptr()
+                desc.feat_bf16_ld = f16.stride(0)
+            setattr(args, name, desc)
+        args.mimic_enabled = 1 if mimic is not None else 0
+        args.b.num_neg = self.num_neg
+        self.csr = None
+        if positives is not None:
+            self.csr = positives_csr(positives, device=self.device, num_users=ue.num_embeddings)
+            if self.csr.max_degree >= self.num_items:
+                raise RuntimeError("a user interacted with all items; cannot sample negatives.")
+            args.b.pos_offsets = self.csr.offsets.data_ptr()
+            args.b.pos_values = self.csr.values.data_ptr()
+        args.b.seed = draw_seed() if seed is None else int(seed)
+        args.num_items_global = self.num_items
+        self.loss_out = torch.zeros(5, dtype=torch.float32, device=self.device)
+        self.loss_accum = torch.zeros(2, dtype=torch.float64, device=self.device)
+        self.status = torch.zeros(1, dtype=torch.int32, device=self.device)
+        args.loss_out = self.loss_out.data_ptr()
+        args.loss_accum = self.loss_accum.data_ptr()
+        args.status = self.status.data_ptr()
+        self.max_batch = int(max_batch)
+        if self.max_batch <= 0:
+            raise ValueError("ttamm: max_batch must be positive")
+        args.b.batch = self.max_batch
+        self.lib = _lib.load()
+        self.ws_bytes = int(self.lib.ttamm_eval_loss_workspace_size(ctypes.byref(args)))
+        self.workspace = torch.empty(self.ws_bytes, dtype=torch.uint8, device=self.device)
+        args.workspace = self.workspace.data_ptr()
+        args.workspace_bytes = self.ws_bytes
+        self.neg_buffer = torch.empty(self.max_batch * self.num_neg, dtype=torch.long, device=self.device)
+        self.args = args
+        self.batches_done = 0
+
+    def step(self, users: torch.Tensor, pos_items: torch.Tensor, neg_items: torch.Tensor | None = None, *,
+             logits_out: torch.Tensor | None = None) -> None:
+        """Enqueue one validation batch on the current stream (no host synchronisation).
+        ``neg_items`` [B, N] injects the negatives (default: drawn on the device into
+        ``neg_buffer``); ``logits_out`` (float32 [B (1 + N)]) receives the logits in the order of
+        ``torch.cat([pos_logits, neg_logits.reshape(-1)])`` (training.py:898)."""
+        B = users.numel()
+        if B == 0:
+            return
+        if B > self.max_batch:
+            raise ValueError("ttamm: batch larger than the step was sized for")
+        if users.dtype != torch.long or pos_items.dtype != torch.long:
+            raise ValueError("Adaptive mimic indices must be torch.long tensors.")
+        if pos_items.numel() != B:
+            raise ValueError("ttamm: one positive item per interaction")
+        _lib.require_rocm(users, "eval loss")
+        _lib.require_rocm(pos_items, "eval loss")
+        a = self.args
+        a.b.users = users.data_ptr()
+        a.b.pos_items = pos_items.data_ptr()
+        a.b.batch = B
+        if neg_items is not None:
+            if neg_items.numel() != B * self.num_neg or neg_items.dtype != torch.long:
+                raise ValueError("ttamm: negatives must be int64 [batch, negatives_per_positive]")
+            _lib.require_rocm(neg_items, "eval loss")
+            a.b.neg_items = neg_items.data_ptr()
+            a.b.sample_negatives = 0
+        else:
+            if self.csr is None:
+                raise ValueError("ttamm: positives are required to sample negatives")
+            a.b.neg_items = self.neg_buffer.data_ptr()
+            a.b.sample_negatives = 1
+        a.b.counter = self.batches_done
+        out = None
+        if logits_out is not None:
+            if logits_out.dtype != torch.float32 or logits_out.numel() != B * (1 + self.num_neg) or \
+                    not logits_out.is_contiguous():
+                raise ValueError("ttamm: logits_out must be a contiguous float32 tensor of batch * (1 + negatives) elements")
+            _lib.require_rocm(logits_out, "eval loss")
+            out = logits_out.data_ptr()
+        _lib.check(self.lib.ttamm_eval_loss(ctypes.byref(a), out, _lib.stream_handle(self.device)))
+        self.batches_done += 1
+
+    def finish(self) -> float:
+        """Synchronise once, surface device-side errors, and return the pass's mean loss weighted
+        by positives (training.py:909-914; 0.0 when nothing ran).  The accumulators, the status word
+        and the batch counter are zeroed, so the engine serves the next loader from scratch."""
+        torch.cuda.current_stream(self.device).synchronize()
+        status = int(self.status.item())
+        total, count = self.loss_accum.tolist()
+        self.loss_accum.zero_()
+        self.status.zero_()
+        self.batches_done = 0
+        if status & _lib.STATUS_INDEX_OUT_OF_RANGE:
+            raise IndexError("index out of range in self")
+        if status & _lib.STATUS_SAMPLER_EXHAUSTED:
+            raise RuntimeError("Exceeded resampling attempts while drawing negatives.")
+        return total / count if count > 0 else 0.0
+
+    def last_loss(self) -> float:
+        """The last batch's BCE (synchronises)."""
+        return float(self.loss_out[1].item())
+
+
+def compute_loss(
+    model: TwoTowerModel,
+    dataloader: Iterable,
+    *,
+    criterion: nn.BCEWithLogitsLoss,
+    negatives_per_positive: int,
+    num_items: int,
+    user_positive_items: Mapping[int, set[int]],
+    user_features: torch.Tensor | None,
+    item_features: torch.Tensor | None,
+    device: torch.device,
+    batch_hook: Callable[[int, torch.Tensor, torch.Tensor], Any] | None = None,
+    seed: int | None = None,
+) -> float:
+    """Drop-in for ``_compute_loss`` (training.py:836-914) executed on the MI355X: the model is put
+    (and left) in eval mode, every batch is one ``ttamm_eval_loss`` call with no host
+    synchronisation, and the pass synchronises once at its end — where an out-of-range id
+    (IndexError) or sampler exhaustion (RuntimeError) surfaces.
+
+    ``batch_hook(step, users, pos)`` has ``train_one_epoch``'s signature: its first result, if not
+    None, is the batch's negatives [B, N] (instead of the on-device sampler); a second element is
+    ignored.  ``seed`` keys the sampler's Philox stream (default: drawn from torch's generator)."""
+    model.eval()
+    if not isinstance(criterion, nn.BCEWithLogitsLoss) or criterion.reduction != "mean" or \
+            criterion.weight is not None or criterion.pos_weight is not None:
+        raise NotImplementedError("ttamm: the step implements BCEWithLogitsLoss(reduction='mean')")
+    if num_items != model.item_encoder.num_embeddings:
+        raise ValueError("num_items does not match the item embedding table")
+    device = torch.device(device)
+    engine = None
+    step = 0
+    for users_in, pos_in in dataloader:
+        users = users_in.to(device, non_blocking=True).reshape(-1)
+        pos = pos_in.to(device, non_blocking=True).reshape(-1)
+        if engine is None:
+            size = getattr(dataloader, "batch_size", None) or users.numel()
+            engine = FusedEvalLoss(
+                model, negatives_per_positive=negatives_per_positive, positives=user_positive_items,
+                user_features=user_features, item_features=item_features,
+                max_batch=max(int(size), users.numel()), seed=seed,
+            )
+        neg = None
+        if batch_hook is not None:
+            res = batch_hook(step, users_in, pos_in)
+            neg = res[0] if isinstance(res, (tuple, list)) else res
+            if neg is not None:
+                neg = neg.to(device, torch.long).reshape(-1)
+        engine.step(users, pos, neg)  # stream-ordered: inputs are recycled safely
         step += 1
     if engine is None:
         return 0.0
