@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define TTAMM_ABI_VERSION 26
+#define TTAMM_ABI_VERSION 27
 
 #define TTAMM_OK 0
 #define TTAMM_E_INVALID 1 /* bad shape / config / dtype  -> ValueError   */
@@ -476,6 +476,43 @@ int ttamm_candidate_topk(const float* queries, int64_t n_queries, int64_t ldq, c
                          int64_t ldi, int32_t dim, const int64_t* cand_offsets, const int64_t* cand_rows,
                          int32_t max_candidates, int32_t cosine, int32_t k, float* out_scores, int64_t* out_positions,
                          void* stream);
+
+/* ---- ranking metrics (the metric half of the epoch's evaluation) ---------------------------
+ * Replaces per_user_metrics / compute_ranking_metrics (src/evaluation/metrics.py:49-71, :74-116)
+ * and the per-user list building around them in _evaluate_model (training.py:963-972) for every
+ * query at once.  Query q's prediction is row q of pred_ids [n_queries, k_pred] (leading dim
+ * ld_pred; the ids ttamm_retrieval_topk / a gather of ttamm_candidate_topk's positions left in
+ * HBM), its ground truth truth_values[truth_offsets[q] .. truth_offsets[q + 1]).
+ * Preconditions: truth_offsets non-decreasing and inside truth_values; each query's truth
+ * segment sorted ascending and unique (the set of metrics.py:87-88).  Rules, in order:
+ *   - ids < 0 are dropped wherever they occur and the rest keep their order (the filter of
+ *     training.py:963); only the first max_k = max(k_values) kept ids are looked at (:57, :66);
+ *   - pad_with_truth != 0 and fewer than max_k ids kept: the query's truth items not listed yet
+ *     follow the list, which is then cut to max_k (training.py:969-972; every appended item is
+ *     relevant, so their order changes no metric);
+ *   - recall@k = hits / max(T, 1), precision@k = hits / max(k, 1), hit_rate@k = hits > 0 with
+ *     hits = len(set(head) & truth): a repeated id counts once (metrics.py:58-62), T the truth size;
+ *   - ndcg@k = dcg / idcg(min(k, T)), 0 when idcg is 0, discounts 1 / log2(i + 2) summed left to
+ *     right over EVERY relevant position (:22-34); map@k = sum(running hits / position) /
+ *     min(T, k) (:37-46); mrr = 1 / first relevant position within max_k, else 0 (:65-70);
+ *   - a query with an empty truth segment is not counted (:88-90): its row is all zero.
+ * All arithmetic is fp64; the discount and ideal-DCG tables are built on the host with log2.
+ * Row layout, k_values (host array, any order) as given: columns 5 j .. 5 j + 4 = recall,
+ * precision, ndcg, hit_rate, map at k_values[j]; column 5 n_k = mrr.  per_user (optional) receives
+ * every query's row; summary [5 n_k + 2] the column means over the counted queries (np.mean of
+ * :101-105; 0 when none is counted) and then the count.  The means are summed in a fixed order
+ * (256-query chunks, chunks in index order, no float atomics): the same inputs give the same bits.
+ * TTAMM_E_INVALID, before any device work: n_k outside [1, 8], a k outside [1, 192], k_pred
+ * outside [0, 192], ld_pred < k_pred, ld_per_user < 5 n_k + 1 with per_user given, NULL summary /
+ * truth_offsets / workspace, NULL pred_ids with k_pred > 0 and n_queries > 0, a workspace smaller
+ * than ttamm_ranking_metrics_workspace_size.  n_queries == 0 writes a zero summary. */
+size_t ttamm_ranking_metrics_workspace_size(int64_t n_queries, int32_t n_k);
+int ttamm_ranking_metrics(const int64_t* pred_ids, int64_t n_queries, int32_t k_pred, int64_t ld_pred,
+                          const int64_t* truth_offsets /* [n_queries + 1] */, const int64_t* truth_values,
+                          const int32_t* k_values /* host, [n_k] */, int32_t n_k, int32_t pad_with_truth,
+                          double* per_user /* [n_queries, ld_per_user] or NULL */, int64_t ld_per_user,
+                          double* summary /* [5 n_k + 2] */, void* workspace, size_t workspace_bytes,
+                          void* stream);
 
 /* dst[r, c] = bf16(src[r, c]) rounded to nearest even for c < cols, 0 for cols <= c < ld_dst: the
  * bf16 feature copy of a matmul_bf16 tower (ttamm_tower.features_bf16). */

@@ -94,6 +94,21 @@ TTAMM_API int ttamm_candidate_topk(const float* queries, int64_t n_queries, int6
                                  max_candidates, cosine, k, out_scores, out_positions, (hipStream_t)stream);
 }
 
+TTAMM_API size_t ttamm_ranking_metrics_workspace_size(int64_t n_queries, int32_t n_k) {
+    return ranking_metrics_workspace_bytes(n_queries, n_k);
+}
+
+TTAMM_API int ttamm_ranking_metrics(const int64_t* pred_ids, int64_t n_queries, int32_t k_pred, int64_t ld_pred,
+                                    const int64_t* truth_offsets, const int64_t* truth_values,
+                                    const int32_t* k_values, int32_t n_k, int32_t pad_with_truth, double* per_user,
+                                    int64_t ld_per_user, double* summary, void* workspace, size_t workspace_bytes,
+                                    void* stream) {
+    g_last_error.clear();
+    return launch_ranking_metrics(pred_ids, n_queries, k_pred, ld_pred, truth_offsets, truth_values, k_values, n_k,
+                                  pad_with_truth, per_user, ld_per_user, summary, workspace, workspace_bytes,
+                                  (hipStream_t)stream);
+}
+
 TTAMM_API int ttamm_to_bf16(const float* src, int64_t rows, int32_t cols, int64_t ld_src, uint16_t* dst,
                             int64_t ld_dst, void* stream) {
     g_last_error.clear();

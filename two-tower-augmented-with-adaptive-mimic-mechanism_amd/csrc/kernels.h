@@ -429,6 +429,17 @@ int launch_retrieval_topk(const float* Q, int64_t nq, int64_t ldq, const float* 
                           size_t ws_bytes, hipStream_t s);
 
 // ------------------------------------------------------------------------------------
+// Ranking metrics of predicted id rows against ground-truth CSR segments (metrics.hip)
+// ------------------------------------------------------------------------------------
+constexpr int kMetricsMaxK = 192;   // list positions looked at (the top-k kernels' limit)
+constexpr int kMetricsMaxNk = 8;    // k values per call
+constexpr int kMetricsMaxCols = 5 * kMetricsMaxNk + 1;  // five metrics per k, then mrr
+size_t ranking_metrics_workspace_bytes(int64_t nq, int n_k);
+int launch_ranking_metrics(const int64_t* pred, int64_t nq, int k_pred, int64_t ld_pred, const int64_t* toff,
+                           const int64_t* tval, const int32_t* ks, int n_k, int pad, double* per_user,
+                           int64_t ld_per_user, double* summary, void* ws, size_t ws_bytes, hipStream_t s);
+
+// ------------------------------------------------------------------------------------
 // Coalesce + optimizers (optim.hip)
 // ------------------------------------------------------------------------------------
 // Grouping of a batch's row ids ("coalesce": duplicates summed in batch order, as torch's

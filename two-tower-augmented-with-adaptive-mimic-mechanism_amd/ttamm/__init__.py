@@ -15,6 +15,7 @@ from .encoders import (
     build_tower_encoder,
 )
 from .inbatch import inbatch_bce
+from .metrics import RankingMetrics, compute_ranking_metrics, evaluate_metrics, ranking_metrics
 from .retrieval import encode_item_embeddings, evaluate_model, prepare_faiss_resources
 from .samplers import PositivesCSR, sample_negative_items
 from .training import (
@@ -37,18 +38,22 @@ __all__ = [
     "FusedEvalLoss",
     "FusedTrainStep",
     "PositivesCSR",
+    "RankingMetrics",
     "TowerEncoder",
     "TwoTowerModel",
     "build_feature_encoder",
     "build_id_embedding",
     "build_tower_encoder",
     "compute_loss",
+    "compute_ranking_metrics",
     "encode_item_embeddings",
+    "evaluate_metrics",
     "evaluate_model",
     "inbatch_bce",
     "load_features",
     "load_interactions",
     "prepare_faiss_resources",
+    "ranking_metrics",
     "sample_negative_items",
     "save_features",
     "save_interactions",

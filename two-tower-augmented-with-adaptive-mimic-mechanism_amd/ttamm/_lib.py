@@ -185,7 +185,7 @@ class StepArgs(ctypes.Structure):
     ]
 
 
-ABI_VERSION = 26  # ttamm.h TTAMM_ABI_VERSION
+ABI_VERSION = 27  # ttamm.h TTAMM_ABI_VERSION
 G0_EXACT = 0  # ttamm.h TTAMM_G0_EXACT
 DENSE_ADAM = 0  # ttamm.h TTAMM_DENSE_ADAM
 DENSE_SGD = 1  # ttamm.h TTAMM_DENSE_SGD
@@ -239,6 +239,12 @@ SIGNATURES = {
     "ttamm_retrieval_topk": (
         ctypes.c_int,
         [c_vp, c_i64, c_i64, c_vp, c_i64, c_i64, c_i32, c_vp, c_vp, c_i32, c_vp, c_vp, c_vp, ctypes.c_size_t, c_vp],
+    ),
+    "ttamm_ranking_metrics_workspace_size": (ctypes.c_size_t, [c_i64, c_i32]),
+    "ttamm_ranking_metrics": (
+        ctypes.c_int,
+        [c_vp, c_i64, c_i32, c_i64, c_vp, c_vp, ctypes.POINTER(c_i32), c_i32, c_i32, c_vp, c_i64, c_vp, c_vp,
+         ctypes.c_size_t, c_vp],
     ),
     "ttamm_flush_tables": (ctypes.c_int, [ctypes.POINTER(StepArgs), c_vp]),
     "ttamm_gather_rows": (ctypes.c_int, [c_vp, c_i64, c_i32, c_vp, c_i64, c_vp, c_i64, c_vp]),

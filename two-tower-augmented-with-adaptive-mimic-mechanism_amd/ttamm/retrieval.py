@@ -207,10 +207,12 @@ def sampled_candidates(users: Sequence[int], truth: Mapping[int, set[int]], bloc
     return lists
 
 
-def _evaluate_sampled(model, users: list[int], truth: dict[int, set[int]], blocked: Mapping[int, Iterable[int]], *,
-                      item_features, user_features, device, num_items: int, candidate_samples: int, max_k: int,
-                      rng: np.random.Generator) -> dict[int, list[int]]:
-    """_retrieve_with_sampling for every user in one launch (ttamm_candidate_topk)."""
+def _sampled_topk(model, users: list[int], truth: dict[int, set[int]], blocked: Mapping[int, Iterable[int]], *,
+                  item_features, user_features, device, num_items: int, candidate_samples: int, max_k: int,
+                  rng: np.random.Generator) -> tuple[list[list[int]], np.ndarray, np.ndarray, torch.Tensor]:
+    """_retrieve_with_sampling for every user in one launch (ttamm_candidate_topk): the candidate
+    lists (host, the reference's draw order), their concatenation and CSR offsets, and the device
+    tensor [len(users), max_k] of each user's best LIST POSITIONS (-1 past a short list)."""
     lists = sampled_candidates(users, truth, blocked, num_items=num_items, candidate_samples=candidate_samples, rng=rng)
     flat = np.fromiter((i for c in lists for i in c), dtype=np.int64)
     offsets = np.zeros(len(lists) + 1, dtype=np.int64)
@@ -233,6 +235,12 @@ def _evaluate_sampled(model, users: list[int], truth: dict[int, set[int]], block
         items.stride(0) if items.numel() else q.shape[1], q.shape[1], off_d.data_ptr(),
         rows_d.data_ptr() if rows_d.numel() else None, most, cosine, k, scores.data_ptr(), pos.data_ptr(),
         _lib.stream_handle(device)))
+    return lists, flat, offsets, pos
+
+
+def _evaluate_sampled(model, users: list[int], truth: dict[int, set[int]], blocked: Mapping[int, Iterable[int]], *,
+                      max_k: int, **kw) -> dict[int, list[int]]:
+    lists, _, _, pos = _sampled_topk(model, users, truth, blocked, max_k=max_k, **kw)
     preds: dict[int, list[int]] = {}
     for u, cand, prow in zip(users, lists, pos.cpu().tolist()):
         preds[u] = [cand[p] for p in prow[: min(max_k, len(cand))]]
@@ -290,22 +298,30 @@ def evaluate_model(
         return _evaluate_sampled(model, users, truth, train_positive_map, item_features=item_feature_tensor,
                                  user_features=user_feature_tensor, device=device, num_items=num_items,
                                  candidate_samples=candidate_samples, max_k=max_k, rng=rng), truth
+    q, item_embeddings = _exact_operands(model, torch.tensor(users, dtype=torch.long, device=device),
+                                         faiss_resources=faiss_resources, item_embeddings=item_embeddings,
+                                         item_feature_tensor=item_feature_tensor,
+                                         user_feature_tensor=user_feature_tensor, device=device, num_items=num_items)
+    return _exact(users, truth, q, item_embeddings, train_positive_map, max_k, device), truth
+
+
+def _exact_operands(model, users: torch.Tensor, *, faiss_resources, item_embeddings, item_feature_tensor,
+                    user_feature_tensor, device, num_items: int) -> tuple[torch.Tensor, torch.Tensor]:
+    """(queries, item matrix) of the exact search, as _evaluate_model picks them (:940-955)."""
     if faiss_resources is not None and item_embeddings is None:
         item_embeddings = faiss_resources["index"]
         if faiss_resources.get("normalize"):  # already normalised; the queries still need it
-            q = encode_user_embeddings(model, torch.tensor(users, dtype=torch.long, device=device),
-                                       user_features=user_feature_tensor)
+            q = encode_user_embeddings(model, users, user_features=user_feature_tensor)
             normalize_rows(q)
-            return _exact(users, truth, q, item_embeddings, train_positive_map, max_k, device), truth
+            return q, item_embeddings
     if item_embeddings is None:
         item_embeddings = encode_item_embeddings(model, num_items=num_items, item_features=item_feature_tensor,
                                                  device=device)
-    q = encode_user_embeddings(model, torch.tensor(users, dtype=torch.long, device=device),
-                               user_features=user_feature_tensor)
+    q = encode_user_embeddings(model, users, user_features=user_feature_tensor)
     if _uses_cosine(model):  # normalize_L2 on the index (:670-672) and on every query (:954-955)
         item_embeddings = normalize_rows(item_embeddings.clone())
         normalize_rows(q)
-    return _exact(users, truth, q, item_embeddings, train_positive_map, max_k, device), truth
+    return q, item_embeddings
 
 
 def _exact(users, truth, q, item_embeddings, train_positive_map, max_k, device) -> dict[int, list[int]]:
