@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define TTAMM_ABI_VERSION 27
+#define TTAMM_ABI_VERSION 28
 
 #define TTAMM_OK 0
 #define TTAMM_E_INVALID 1 /* bad shape / config / dtype  -> ValueError   */
@@ -436,6 +436,31 @@ int ttamm_exchange_compact_supported(const ttamm_step_args* args);
 size_t ttamm_eval_loss_workspace_size(const ttamm_step_args* args);
 int ttamm_eval_loss(const ttamm_step_args* args, float* logits_out /* [batch*(1+num_neg)] or NULL */, void* stream);
 
+/* One validation batch in in-batch mode (ttamm's own definition, not reference behaviour:
+ * oracle/cpu_reference.py train_step(in_batch=True) evaluated in eval mode).  The towers, the
+ * augment, the sampler and the staging are ttamm_eval_loss's; the logits are S = U P^T
+ * [batch, batch] with label 1 on the diagonal (inbatch_loss_kernel on the augmented user rows and
+ * the positives' rows: the forward third of the training kernel, nothing batch x batch stored)
+ * and the b.num_neg >= 0 sampled negatives' <U_b, n_bj> with label 0; the loss is one
+ * BCEWithLogits mean over all batch * (batch + num_neg) logits.  No mimic terms, no L_cal.  A
+ * fixed launch sequence on the caller's stream with no host read.
+ *   read:     the fields ttamm_eval_loss reads, with the same conventions.  With b.num_neg == 0
+ *             there is no sampler launch and no negative row (b.neg_items, b.sample_negatives,
+ *             pos_offsets / pos_values are not used).
+ *   ignored:  in_batch (not consulted), and every field ttamm_eval_loss ignores.
+ *   rejected: phase != TTAMM_PHASE_ALL, b.num_neg outside [0, 64], an embedding dim that is not
+ *             a multiple of 4 or is above 128, an empty batch, NULL loss_out / status / workspace,
+ *             a workspace smaller than ttamm_eval_loss_inbatch_workspace_size (TTAMM_E_INVALID,
+ *             before any device work).
+ * loss_out, loss_accum and the status rule are ttamm_eval_loss's.  bce = (the scorer's block
+ * partials + the in-batch kernel's block partials, each in block order) / (batch * (batch +
+ * num_neg)): no float atomics, the same inputs give the same bits.  The work split is a function
+ * of the shapes only.  There is no logits_out: S is never stored.  TTAMM_FP32_MFMA=exact is not
+ * honoured by the forward-only kernel (always the split-bf16 products).  The workspace is the
+ * plain pass's plus one float per block of the in-batch kernel (no slab). */
+size_t ttamm_eval_loss_inbatch_workspace_size(const ttamm_step_args* args);
+int ttamm_eval_loss_inbatch(const ttamm_step_args* args, void* stream);
+
 /* Size (floats) of the replicated-weight gradient arena of a sharded step: both towers'
  * feature-encoder and gate weight+bias gradients, contiguous (the all-reduce buffer). */
 int64_t ttamm_dense_grad_floats(const ttamm_step_args* args);
@@ -678,6 +703,22 @@ int ttamm_inbatch_bce(const float* users, int64_t batch, int64_t ldu, const floa
                       int64_t n_positives, int64_t ldp, int32_t dim, int64_t row_base, float inv_count,
                       float* d_users, int64_t ld_du, float* d_positives, int64_t ld_dp, double* loss_sum,
                       void* workspace, size_t workspace_bytes, void* stream);
+
+/* The forward third of ttamm_inbatch_bce: *loss_sum alone, under ttamm_inbatch_bce's contract for
+ * it (fp64 sum of the BCE-with-logits terms of S, label 1 at (b, row_base + b); n_positives >=
+ * batch, row_base the rank's first global position in the all-gathered sharded case).
+ * inbatch_loss_kernel: the user role's score product on split-bf16 MFMA and the training kernel's
+ * per-element BCE arithmetic; no dS, no gradient, no slab, no reduce launch.
+ *   read:     every argument; rows must be 16-byte aligned (ldu, ldp multiples of 4).
+ *   rejected: a NULL pointer, dim not a multiple of 4 or above 128, ldu / ldp < dim, row_base < 0
+ *             or row_base + batch > n_positives, a workspace smaller than
+ *             ttamm_inbatch_loss_workspace_size (TTAMM_E_INVALID, before any device work).
+ * The workspace holds one float per block; the blocks' sums are added in block order (no float
+ * atomics): the same inputs give the same bits.  TTAMM_FP32_MFMA=exact is not honoured. */
+size_t ttamm_inbatch_loss_workspace_size(int64_t batch, int64_t n_positives, int32_t dim);
+int ttamm_inbatch_bce_loss(const float* users, int64_t batch, int64_t ldu, const float* positives,
+                           int64_t n_positives, int64_t ldp, int32_t dim, int64_t row_base, double* loss_sum,
+                           void* workspace, size_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }

@@ -26,6 +26,8 @@ int exchange_compact_supported(const ttamm_step_args& A);
 int flush_tables(const ttamm_step_args& A, hipStream_t s);
 size_t eval_loss_workspace_size(const ttamm_step_args& A);
 int eval_loss(const ttamm_step_args& A, float* logits_out, hipStream_t s);
+size_t eval_loss_inbatch_workspace_size(const ttamm_step_args& A);
+int eval_loss_inbatch(const ttamm_step_args& A, hipStream_t s);
 size_t tower_forward_workspace_size(const ttamm_tower& T, int64_t n);
 int tower_forward_eval(const ttamm_tower& T, const int64_t* idx, const int64_t* fidx, int64_t n, int augment,
                        float* out, void* ws, size_t ws_bytes, hipStream_t s);
@@ -189,6 +191,17 @@ TTAMM_API int ttamm_eval_loss(const ttamm_step_args* args, float* logits_out, vo
     return eval_loss(*args, logits_out, (hipStream_t)stream);
 }
 
+TTAMM_API size_t ttamm_eval_loss_inbatch_workspace_size(const ttamm_step_args* args) {
+    if (!args) return 0;
+    return eval_loss_inbatch_workspace_size(*args);
+}
+
+TTAMM_API int ttamm_eval_loss_inbatch(const ttamm_step_args* args, void* stream) {
+    if (!args) return fail(TTAMM_E_INVALID, "null step args");
+    g_last_error.clear();
+    return eval_loss_inbatch(*args, (hipStream_t)stream);
+}
+
 TTAMM_API int ttamm_gather_rows(const float* table, int64_t table_rows, int32_t dim, const int64_t* idx, int64_t n,
                                 float* out, int64_t out_ld, void* stream) {
     if (n < 0 || dim <= 0 || out_ld < dim || table_rows <= 0) return fail(TTAMM_E_INVALID, "gather_rows: bad shape");
@@ -339,4 +352,17 @@ TTAMM_API int ttamm_inbatch_bce(const float* users, int64_t batch, int64_t ldu, 
     g_last_error.clear();
     return inbatch_standalone(users, batch, ldu, positives, n_positives, ldp, dim, row_base, inv_count, d_users,
                               ld_du, d_positives, ld_dp, loss_sum, workspace, workspace_bytes, (hipStream_t)stream);
+}
+
+TTAMM_API size_t ttamm_inbatch_loss_workspace_size(int64_t batch, int64_t n_positives, int32_t dim) {
+    if (batch <= 0 || n_positives <= 0 || dim <= 0) return 0;
+    return inbatch_loss_workspace_bytes(batch, n_positives, dim);
+}
+
+TTAMM_API int ttamm_inbatch_bce_loss(const float* users, int64_t batch, int64_t ldu, const float* positives,
+                                     int64_t n_positives, int64_t ldp, int32_t dim, int64_t row_base,
+                                     double* loss_sum, void* workspace, size_t workspace_bytes, void* stream) {
+    g_last_error.clear();
+    return inbatch_loss_standalone(users, batch, ldu, positives, n_positives, ldp, dim, row_base, loss_sum, workspace,
+                                   workspace_bytes, (hipStream_t)stream);
 }

@@ -813,6 +813,162 @@ __global__ void ib_loss_sum_kernel(const float* __restrict__ parts, int n, doubl
     if (threadIdx.x == 0) out[0] = red[0];
 }
 
+// ---- forward-only variant: the BCE sum of S, nothing else (validation in in-batch mode) ------------
+// inbatch_x_kernel's user role cut down to product 1 and the BCE terms: a block owns 32 kIblWaves
+// user rows and one split of the columns; a wave keeps its 32 rows' split-bf16 fragments in
+// registers, the positives stream through LDS in 64-row tiles of the same three-plane image
+// (ibx_off, ibx_split) and each 32 x 32 score block is formed by the same five partial products
+// (ibx_mfma6).  Every in-range element then adds its BCE term with the training kernel's
+// arithmetic (one hardware exp2 of -|x|, hardware log2; max(x, 0) + ln(1 + t) on label-free
+// interior blocks), so a batch's training and validation BCE are the same function of the same
+// rows.  No dS, no second product, no transposed LDS reads, no slabs: a block writes one float.
+// Without the dU accumulators and the second product's operands a wave needs fewer than 256
+// registers at every D, so a block is 8 waves (two per SIMD: one wave's elementwise pass runs under
+// the other's MFMAs), alone on its CU with the tile double buffered (96 KB LDS, one barrier per
+// tile, the tile after next in flight in registers) and staged once for 256 rows.
+constexpr int kIblWaves = 8;
+constexpr int kIblRows = 32 * kIblWaves;
+constexpr int kIblBlocks = 256;  // one resident round: a block per CU
+
+template <int DP>
+__global__ __launch_bounds__(64 * kIblWaves, 1) void inbatch_loss_kernel(InBatchLossArgs A) {
+    constexpr int NT = 64 * kIblWaves;
+    constexpr int KS = DP / 16;            // k steps of the score product
+    constexpr int TF4 = kIbTile * DP / 4;  // float4 per column tile
+    constexpr int LOADS = TF4 / NT;
+    static_assert(TF4 % NT == 0, "whole staging rounds");
+    __shared__ __attribute__((aligned(16))) unsigned char tiles[2][3 * kIbxPlane];
+    __shared__ float red[kIblWaves];
+
+    const int blk = blockIdx.x;
+    const int rb = blk / A.splits, sp = blk - rb * A.splits;
+    const float* R = A.U;
+    const float* C = A.P;
+    const int64_t ldr = A.ldu, nr = A.B, ldc = A.ldp, nc = A.Bc;
+    const int64_t c_begin = min(nc, (int64_t)sp * A.cols), c_end = min(nc, c_begin + A.cols);
+    const int D = A.D;
+
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, li = lane & 31, h = lane >> 5;
+    const int64_t r0 = (int64_t)rb * kIblRows + 32 * w;
+
+    // this lane's row fragments (B operand): R[r0 + li][16 s + 8 h + j], zero past D / nr
+    bf16x8_t rf[KS][3];
+    {
+        const int64_t row = r0 + li;
+        const bool rok = row < nr;
+#pragma unroll
+        for (int s = 0; s < KS; ++s) {
+            const int col = 16 * s + 8 * h;
+            const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
+            const float4 a = (rok && col < D) ? *reinterpret_cast<const float4*>(R + row * ldr + col) : z;
+            const float4 b = (rok && col + 4 < D) ? *reinterpret_cast<const float4*>(R + row * ldr + col + 4) : z;
+            uint2 pa[3], pb[3];
+            ibx_split(a, pa);
+            ibx_split(b, pb);
+#pragma unroll
+            for (int q = 0; q < 3; ++q) rf[s][q] = ibx_cat(pa[q], pb[q]);
+        }
+    }
+    float bce = 0.f, bce_lin = 0.f, bce_log2 = 0.f;
+
+    // column tile -> registers (zero past c_end / D) -> the three planes of an LDS image
+    float4 st[LOADS];
+    auto load = [&](int64_t c0) {
+#pragma unroll
+        for (int it = 0; it < LOADS; ++it) {
+            const int lin = tid + it * NT;
+            const int row = lin / (DP / 4), col = (lin - row * (DP / 4)) * 4;
+            const int64_t gc = c0 + row;
+            st[it] = (gc < c_end && col < D) ? *reinterpret_cast<const float4*>(C + gc * ldc + col)
+                                             : make_float4(0.f, 0.f, 0.f, 0.f);
+        }
+    };
+    auto store = [&](unsigned char* dst) {
+#pragma unroll
+        for (int it = 0; it < LOADS; ++it) {
+            const int lin = tid + it * NT;
+            const int row = lin / (DP / 4), c4 = lin - row * (DP / 4);
+            const int o = ibx_off(row, c4 >> 1) + 8 * (c4 & 1);
+            uint2 pl[3];
+            ibx_split(st[it], pl);
+#pragma unroll
+            for (int q = 0; q < 3; ++q) *reinterpret_cast<uint2*>(dst + q * kIbxPlane + o) = pl[q];
+        }
+    };
+
+    const int ntiles = c_end > c_begin ? (int)((c_end - c_begin + kIbTile - 1) / kIbTile) : 0;
+    if (ntiles > 0) {  // tile 0 in buffer 0, tile 1 in flight in registers
+        load(c_begin);
+        store(tiles[0]);
+        if (ntiles > 1) load(c_begin + kIbTile);
+    }
+    __syncthreads();
+    const int64_t gr = r0 + li;
+    const bool row_ok = gr < nr;
+    for (int t = 0; t < ntiles; ++t) {
+        const int64_t c0 = c_begin + (int64_t)t * kIbTile;
+        const unsigned char* const tile = tiles[t & 1];
+        // the label Y = 1 of this lane's user row sits at tile column diag
+        const int64_t dl = A.row_base + gr - c0;
+        const int diag = (dl >= 0 && dl < kIbTile) ? (int)dl : -1;
+        const int cols_here = (int)min((int64_t)kIbTile, c_end - c0);
+        // wave-uniform: the whole 32 x 64 block is interior and label-free (most tiles)
+        const bool fast = cols_here == kIbTile && __builtin_amdgcn_ballot_w64(diag >= 0 || !row_ok) == 0;
+#pragma unroll
+        for (int jc = 0; jc < 2; ++jc) {  // tile rows 32 jc .. 32 jc + 31
+            // S^T block [32 c x 32 u]: lane = user row r0 + li, register r = tile column
+            f32x16 s2;
+#pragma unroll
+            for (int r = 0; r < 16; ++r) s2[r] = 0.f;
+#pragma unroll
+            for (int s = 0; s < KS; ++s) {
+                const int o = ibx_off(32 * jc + li, 2 * s + h);
+                bf16x8_t a[3];
+#pragma unroll
+                for (int q = 0; q < 3; ++q) a[q] = *reinterpret_cast<const bf16x8_t*>(tile + q * kIbxPlane + o);
+                s2 = ibx_mfma6(a, rf[s], s2);
+            }
+            if (fast) {
+                // y = 0 everywhere: the term is max(x, 0) + ln(1 + t), t = exp(-|x|), summed as two
+                // lane sums (the log2 terms scaled by ln 2 once at the end)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const float x = s2[r];
+                    const float tx = __builtin_amdgcn_exp2f(-fabsf(x) * 1.4426950408889634f);
+                    bce_lin += fmaxf(x, 0.f);
+                    bce_log2 += __builtin_amdgcn_logf(1.0f + tx);
+                }
+            } else {
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const int lc = 32 * jc + (r & 3) + 8 * (r >> 2) + 4 * h;
+                    const bool ok = row_ok && lc < cols_here;
+                    const float y = lc == diag ? 1.0f : 0.0f;
+                    const float x = s2[r];
+                    const float tx = __builtin_amdgcn_exp2f(-fabsf(x) * 1.4426950408889634f);
+                    if (ok) bce += (1.0f - y) * x + fmaxf(-x, 0.f) + __builtin_amdgcn_logf(1.0f + tx) * 0.6931471805599453f;
+                }
+            }
+        }
+        // tile t + 1 (landed in registers during this tile's MFMAs) into the other buffer, last
+        // read in tile t - 1 before that tile's barrier; tile t + 2 in flight
+        if (t + 1 < ntiles) {
+            store(tiles[(t + 1) & 1]);
+            if (t + 2 < ntiles) load(c0 + 2 * kIbTile);
+        }
+        __syncthreads();
+    }
+    bce = wave_sum(bce + (bce_lin + bce_log2 * 0.6931471805599453f));
+    if (lane == 0) red[w] = bce;
+    __syncthreads();
+    if (tid == 0) {
+        float sum = 0.f;
+#pragma unroll
+        for (int i = 0; i < kIblWaves; i += 2) sum += red[i] + red[i + 1];
+        A.loss_part[blk] = sum;
+    }
+}
+
 }  // namespace
 
 // Waves per block of the split-bf16 kernel: 4 (128 rows per block, two blocks per CU, one tile
@@ -959,6 +1115,71 @@ int inbatch_standalone(const float* U, int64_t B, int64_t ldu, const float* P, i
     const int rc = launch_inbatch(a, s);
     if (rc != TTAMM_OK) return rc;
     hipLaunchKernelGGL(ib_loss_sum_kernel, dim3(1), dim3(256), 0, s, a.loss_part, a.rblk_u * a.splits_u, loss_sum);
+    TTAMM_LAUNCH_CHECK();
+    return TTAMM_OK;
+}
+
+// ---- forward-only BCE sum (inbatch_loss_kernel) ----------------------------------------------------
+// Row blocks of kIblRows users x column splits of whole 64-column tiles, ~kIblBlocks blocks: one
+// 8-wave block per CU in a single resident round (the kernel's 96 KB of LDS and two waves per SIMD
+// allow one).  A function of the shapes only: no environment variable moves the split.
+void inbatch_loss_plan(int64_t B, int64_t Bc, InBatchLossArgs& a) {
+    a.rblk = (int)ceil_div(B, kIblRows);
+    const int64_t want = std::min<int64_t>(ceil_div(Bc, kIbTile), ceil_div(kIblBlocks, a.rblk));
+    a.cols = ceil_div(ceil_div(Bc, std::max<int64_t>(1, want)), kIbTile) * kIbTile;
+    a.splits = (int)std::max<int64_t>(1, ceil_div(Bc, a.cols));
+}
+
+int inbatch_loss_blocks(int64_t B, int64_t Bc) {
+    InBatchLossArgs a{};
+    inbatch_loss_plan(B, Bc, a);
+    return a.rblk * a.splits;
+}
+
+int inbatch_loss_check(int D) {
+    TTAMM_REQUIRE(D > 0 && D % 4 == 0 && D <= 128, "in-batch negatives: embedding dim must be a multiple of 4, <= 128");
+    return TTAMM_OK;
+}
+
+int launch_inbatch_loss(InBatchLossArgs& a, hipStream_t s) {
+    int rc;
+    if ((rc = inbatch_loss_check(a.D))) return rc;
+    TTAMM_REQUIRE(a.B > 0 && a.Bc > 0 && a.B < (int64_t(1) << 31) && a.Bc < (int64_t(1) << 31), "in-batch: bad batch");
+    TTAMM_REQUIRE(a.ldu % 4 == 0 && a.ldp % 4 == 0 && ((uintptr_t)a.U | (uintptr_t)a.P) % 16 == 0,
+                  "in-batch: rows must be 16-byte aligned");
+    TTAMM_REQUIRE(a.row_base >= 0 && a.row_base + a.B <= a.Bc, "in-batch: the users' labels must lie inside the columns");
+    inbatch_loss_plan(a.B, a.Bc, a);
+    const dim3 g((unsigned)(a.rblk * a.splits)), t(64 * kIblWaves);
+    switch ((a.D + 31) / 32 * 32) {
+        case 32: hipLaunchKernelGGL(inbatch_loss_kernel<32>, g, t, 0, s, a); break;
+        case 64: hipLaunchKernelGGL(inbatch_loss_kernel<64>, g, t, 0, s, a); break;
+        case 96: hipLaunchKernelGGL(inbatch_loss_kernel<96>, g, t, 0, s, a); break;
+        default: hipLaunchKernelGGL(inbatch_loss_kernel<128>, g, t, 0, s, a); break;
+    }
+    TTAMM_LAUNCH_CHECK();
+    return TTAMM_OK;
+}
+
+size_t inbatch_loss_workspace_bytes(int64_t B, int64_t Bc, int D) {
+    (void)D;
+    return sizeof(float) * (size_t)inbatch_loss_blocks(B, Bc);
+}
+
+int inbatch_loss_standalone(const float* U, int64_t B, int64_t ldu, const float* P, int64_t Bc, int64_t ldp, int D,
+                            int64_t row_base, double* loss_sum, void* ws, size_t ws_bytes, hipStream_t s) {
+    TTAMM_REQUIRE(U && P && loss_sum && ws, "inbatch_bce_loss: null argument");
+    TTAMM_REQUIRE(B > 0 && Bc > 0 && D > 0 && ldu >= D && ldp >= D, "inbatch_bce_loss: bad shape");
+    TTAMM_REQUIRE(row_base >= 0 && row_base + B <= Bc,
+                  "inbatch_bce_loss: row_base must place the B users' labels inside the Bc columns (0 <= row_base, "
+                  "row_base + B <= Bc)");
+    TTAMM_REQUIRE(ws_bytes >= inbatch_loss_workspace_bytes(B, Bc, D), "inbatch_bce_loss: workspace too small");
+    InBatchLossArgs a{};
+    a.U = U, a.ldu = ldu, a.B = B, a.P = P, a.ldp = ldp, a.Bc = Bc, a.D = D;
+    a.row_base = row_base;
+    a.loss_part = static_cast<float*>(ws);
+    const int rc = launch_inbatch_loss(a, s);
+    if (rc != TTAMM_OK) return rc;
+    hipLaunchKernelGGL(ib_loss_sum_kernel, dim3(1), dim3(256), 0, s, a.loss_part, a.rblk * a.splits, loss_sum);
     TTAMM_LAUNCH_CHECK();
     return TTAMM_OK;
 }

@@ -357,6 +357,7 @@ struct EvalScoreArgs {
     float* partials;        // [blocks]: per-block sums of the BCE terms
     int blocks;             // score_blocks(B, D)
     float* logits;          // [B(1+N)] = cat([pos_logits, neg_logits.reshape(-1)]) (training.py:898), or null
+    int skip_pos;           // in-batch validation: the positive logit belongs to S, leave it out of the sum
 };
 int score_eval_check(int N, int D);  // the scorer's limits: 1 <= N <= 64, D <= 512
 int launch_score_eval(const EvalScoreArgs& a, hipStream_t s);
@@ -364,6 +365,11 @@ int launch_score_eval(const EvalScoreArgs& a, hipStream_t s);
 // writes nothing when *status != 0
 int launch_eval_loss_finalize(const float* partials, int blocks, int64_t count, int64_t B, float* loss_out,
                               double* loss_accum, const uint32_t* status, hipStream_t s);
+// the same with bce = (sum of partials + sum of ib_partials) / count (in-batch validation;
+// blocks == 0: no sampled negatives)
+int launch_eval_loss_inbatch_finalize(const float* partials, int blocks, const float* ib_partials, int ib_blocks,
+                                      int64_t count, int64_t B, float* loss_out, double* loss_accum,
+                                      const uint32_t* status, hipStream_t s);
 // bce = (sum of the score partials + sum of ib_partials) / bce_count
 int launch_loss_finalize(const float* partials, int blocks, const float* ib_partials, int ib_blocks, int64_t bce_count,
                          int64_t B, int64_t Bg, int D, float lambda_u, float lambda_i, int mimic, const float* cal,
@@ -398,6 +404,27 @@ size_t inbatch_standalone_workspace_bytes(int64_t B, int64_t Bc, int D);
 int inbatch_standalone(const float* U, int64_t B, int64_t ldu, const float* P, int64_t Bc, int64_t ldp, int D,
                        int64_t row_base, float inv_T, float* dU, int64_t ld_du, float* dP, int64_t ld_dp,
                        double* loss_sum, void* ws, size_t ws_bytes, hipStream_t s);
+// Forward only: the BCE terms of S summed per block, no dS / dU / dP (inbatch_loss_kernel; the
+// validation pass in in-batch mode).  Always the split-bf16 products (TTAMM_FP32_MFMA is not read).
+struct InBatchLossArgs {
+    const float* U;      // [B, ldu] augmented user rows (rows of S)
+    int64_t ldu, B;
+    const float* P;      // [Bc, ldp] augmented positive rows (columns of S)
+    int64_t ldp, Bc;
+    int D;
+    int64_t row_base;    // column of user 0's own positive
+    float* loss_part;    // [rblk * splits] BCE sums of the blocks
+    // filled by inbatch_loss_plan
+    int rblk, splits;
+    int64_t cols;
+};
+void inbatch_loss_plan(int64_t B, int64_t Bc, InBatchLossArgs& a);
+int inbatch_loss_blocks(int64_t B, int64_t Bc);  // floats of loss_part
+int inbatch_loss_check(int D);                   // the kernel's limits: D % 4 == 0, D <= 128
+int launch_inbatch_loss(InBatchLossArgs& a, hipStream_t s);
+size_t inbatch_loss_workspace_bytes(int64_t B, int64_t Bc, int D);
+int inbatch_loss_standalone(const float* U, int64_t B, int64_t ldu, const float* P, int64_t Bc, int64_t ldp, int D,
+                            int64_t row_base, double* loss_sum, void* ws, size_t ws_bytes, hipStream_t s);
 
 // ------------------------------------------------------------------------------------
 // Exact inner-product retrieval + top-k (retrieval.hip)

@@ -562,7 +562,7 @@ __global__ __launch_bounds__(64 * kScoreWaves) void score_eval_kernel(EvalScoreA
         for (int c = 0; c < NCH; ++c)
             if (ok[c]) dot += u[c] * p[c];
         const float sp = wave_sum(dot);
-        bce += bce_logit(sp, 1.0f);
+        if (!A.skip_pos) bce += bce_logit(sp, 1.0f);
         if (A.logits && lane == 0) A.logits[b] = sp;
         for (int j0 = 0; j0 < N; j0 += kScoreNG) {
             const int ng = N - j0 < kScoreNG ? N - j0 : kScoreNG;
@@ -624,7 +624,7 @@ __global__ __launch_bounds__(64 * kScoreWaves) void score_eval_v_kernel(EvalScor
 #pragma unroll
         for (int i = 0; i < NV; ++i) dot += dot4(u[i], p[i]);
         const float sp = group_sum(dot, G);
-        bce += bce_logit(sp, 1.0f);
+        if (!A.skip_pos) bce += bce_logit(sp, 1.0f);
         if (A.logits && s == 0) A.logits[b] = sp;
         for (int j0 = 0; j0 < N; j0 += NG) {
             const int ng = N - j0 < NG ? N - j0 : NG;
@@ -671,6 +671,37 @@ __global__ void eval_loss_finalize_kernel(const float* __restrict__ partials, in
     __shared__ float red[256];
     float s = 0.f;
     for (int i = threadIdx.x; i < blocks; i += blockDim.x) s += partials[i];
+    red[threadIdx.x] = s;
+    __syncthreads();
+    for (int o = blockDim.x / 2; o > 0; o >>= 1) {
+        if (threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0 && *status == 0u) {
+        const float bce = red[0] / (float)count;
+        loss_out[0] = bce;
+        loss_out[1] = bce;
+        loss_out[2] = 0.f;
+        loss_out[3] = 0.f;
+        loss_out[4] = 0.f;
+        if (loss_accum) {
+            loss_accum[0] += (double)bce * (double)B;
+            loss_accum[1] += (double)B;
+        }
+    }
+}
+
+// The in-batch validation batch (ttamm_eval_loss_inbatch): the scorer's partials (the sampled
+// negatives' terms; blocks == 0 without negatives) and inbatch_loss_kernel's, each in block order,
+// then one tree; the same outputs and status rule.
+__global__ void eval_loss_inbatch_finalize_kernel(const float* __restrict__ partials, int blocks,
+                                                  const float* __restrict__ ib_partials, int ib_blocks, int64_t count,
+                                                  int64_t B, float* __restrict__ loss_out,
+                                                  double* __restrict__ loss_accum, const uint32_t* __restrict__ status) {
+    __shared__ float red[256];
+    float s = 0.f;
+    for (int i = threadIdx.x; i < blocks; i += blockDim.x) s += partials[i];
+    for (int i = threadIdx.x; i < ib_blocks; i += blockDim.x) s += ib_partials[i];
     red[threadIdx.x] = s;
     __syncthreads();
     for (int o = blockDim.x / 2; o > 0; o >>= 1) {
@@ -1050,6 +1081,18 @@ int launch_eval_loss_finalize(const float* partials, int blocks, int64_t count, 
     TTAMM_REQUIRE(partials && blocks > 0 && count > 0 && loss_out && status, "eval loss finalize: bad arguments");
     hipLaunchKernelGGL(eval_loss_finalize_kernel, dim3(1), dim3(256), 0, s, partials, blocks, count, B, loss_out,
                        loss_accum, status);
+    TTAMM_LAUNCH_CHECK();
+    return TTAMM_OK;
+}
+
+int launch_eval_loss_inbatch_finalize(const float* partials, int blocks, const float* ib_partials, int ib_blocks,
+                                      int64_t count, int64_t B, float* loss_out, double* loss_accum,
+                                      const uint32_t* status, hipStream_t s) {
+    TTAMM_REQUIRE((blocks == 0 || partials) && blocks >= 0 && ib_partials && ib_blocks > 0 && count > 0 && loss_out &&
+                      status,
+                  "eval loss finalize: bad arguments");
+    hipLaunchKernelGGL(eval_loss_inbatch_finalize_kernel, dim3(1), dim3(256), 0, s, partials, blocks, ib_partials,
+                       ib_blocks, count, B, loss_out, loss_accum, status);
     TTAMM_LAUNCH_CHECK();
     return TTAMM_OK;
 }

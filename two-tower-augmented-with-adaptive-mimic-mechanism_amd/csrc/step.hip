@@ -2286,11 +2286,14 @@ struct EvalWs {
     TowerWs user, item;
     float* partials = nullptr;
     int blocks = 0;
+    float* ib_partials = nullptr;  // in-batch pass: inbatch_loss_kernel's block sums
+    int ib_blocks = 0;
 };
 
 // Forward buffers for B and B(1+N) rows, the staged ids, the weight pads / images the forward
-// forms and the score partials: no backward buffer, gradient slab or coalesce scratch.
-void plan_eval(Arena& ar, const ttamm_step_args& A, EvalWs& ws) {
+// forms and the score partials: no backward buffer, gradient slab or coalesce scratch.  The
+// in-batch pass adds its kernel's block partials (nothing B x B, no slab).
+void plan_eval(Arena& ar, const ttamm_step_args& A, EvalWs& ws, bool in_batch = false) {
     const int64_t B = A.b.batch;
     const int N = A.b.num_neg;
     const int D = out_dim(A.user);
@@ -2326,9 +2329,13 @@ void plan_eval(Arena& ar, const ttamm_step_args& A, EvalWs& ws) {
     tower(A.item, ws.item, B * (1 + (int64_t)N));
     ws.blocks = score_blocks(B, D);
     ws.partials = ar.take<float>((size_t)ws.blocks);
+    if (in_batch) {
+        ws.ib_blocks = inbatch_loss_blocks(B, B);
+        ws.ib_partials = ar.take<float>((size_t)ws.ib_blocks);
+    }
 }
 
-int validate_eval(const ttamm_step_args& A) {
+int validate_eval(const ttamm_step_args& A, bool in_batch = false) {
     const int D = out_dim(A.user);
     int rc;
     if ((rc = validate_tower(A.user, "user_encoder", D, false))) return rc;
@@ -2336,8 +2343,14 @@ int validate_eval(const ttamm_step_args& A) {
     TTAMM_REQUIRE(out_dim(A.item) == D, "User and item encoders must produce embeddings with the same dimension.");
     TTAMM_REQUIRE(A.user.matmul_bf16 == A.item.matmul_bf16, "user and item towers must share one matmul precision");
     TTAMM_REQUIRE(A.phase == TTAMM_PHASE_ALL, "eval loss: phase must be 0, the whole batch in one call (no sharded validation pass)");
-    TTAMM_REQUIRE(A.in_batch == 0, "eval loss: in_batch must be 0 (_compute_loss scores sampled negatives only)");
-    if ((rc = score_eval_check(A.b.num_neg, D))) return rc;
+    if (in_batch) {  // ttamm_eval_loss_inbatch: the in_batch field is not consulted, N = 0 is legal
+        TTAMM_REQUIRE(A.b.num_neg >= 0 && A.b.num_neg <= 64,
+                      "eval loss (in-batch): b.num_neg (negatives_per_positive) must be in [0, 64]");
+        if ((rc = inbatch_loss_check(D))) return rc;
+    } else {
+        TTAMM_REQUIRE(A.in_batch == 0, "eval loss: in_batch must be 0 (_compute_loss scores sampled negatives only)");
+        if ((rc = score_eval_check(A.b.num_neg, D))) return rc;
+    }
     TTAMM_REQUIRE(A.b.batch > 0, "empty batch");
     if (A.mimic_enabled) {
         TTAMM_REQUIRE(A.user.mimic.weight && A.item.mimic.weight, "mimic tables missing");
@@ -2356,9 +2369,20 @@ size_t eval_loss_workspace_size(const ttamm_step_args& A) {
     return ar.off + 256;
 }
 
-int eval_loss(const ttamm_step_args& A, float* logits_out, hipStream_t s) {
+size_t eval_loss_inbatch_workspace_size(const ttamm_step_args& A) {
+    if (A.b.batch <= 0 || A.b.num_neg < 0) return 0;
+    Arena ar{nullptr, 0, 0, true};
+    EvalWs ws;
+    plan_eval(ar, A, ws, true);
+    return ar.off + 256;
+}
+
+// in_batch: ttamm_eval_loss_inbatch — the positives' logits come from S = U P^T
+// (inbatch_loss_kernel on U.aug and I.aug rows [0, B)), the scorer adds the sampled negatives'
+// terms only (none with N == 0) and one finalize divides by B (B + N).
+static int eval_loss_run(const ttamm_step_args& A, float* logits_out, bool in_batch, hipStream_t s) {
     int rc;
-    if ((rc = validate_eval(A))) return rc;
+    if ((rc = validate_eval(A, in_batch))) return rc;
     TTAMM_REQUIRE(A.loss_out && A.status && A.workspace, "eval loss: loss_out, status and workspace are required");
     TTAMM_REQUIRE(A.b.users && A.b.pos_items, "eval loss: b.users / b.pos_items missing");
     const int D = out_dim(A.user);
@@ -2367,12 +2391,12 @@ int eval_loss(const ttamm_step_args& A, float* logits_out, hipStream_t s) {
     const int N = A.b.num_neg;
     EvalWs ws;
     Arena ar{static_cast<char*>(A.workspace), A.workspace_bytes, 0, false};
-    plan_eval(ar, A, ws);
+    plan_eval(ar, A, ws, in_batch);
     TTAMM_REQUIRE(ar.ok(), "workspace too small for this eval loss batch");
     TowerWs &U = ws.user, &I = ws.item;
     int64_t* neg_rows = I.idx_own + B;
     const int64_t* neg_src = A.b.neg_items;
-    if (A.b.sample_negatives) {  // the training step's draws for (seed, counter, row_base)
+    if (A.b.sample_negatives && N > 0) {  // the training step's draws for (seed, counter, row_base)
         const int64_t num_items = A.num_items_global > 0 ? A.num_items_global : A.item.id.rows;
         int64_t* dst = A.b.neg_items ? A.b.neg_items : neg_rows;
         if ((rc = launch_sample_negatives(A.b.users, B, N, num_items, A.b.pos_offsets, A.b.pos_values, A.user.id.rows,
@@ -2380,14 +2404,14 @@ int eval_loss(const ttamm_step_args& A, float* logits_out, hipStream_t s) {
             return rc;
         neg_src = dst;
     }
-    TTAMM_REQUIRE(neg_src != nullptr, "negatives must be given when sample_negatives == 0");
+    TTAMM_REQUIRE(N == 0 || neg_src != nullptr, "negatives must be given when sample_negatives == 0");
     {
         StageArgs st;
         std::memset(&st, 0, sizeof(st));
         st.status = A.status;
         st.seg[st.count++] = StageSeg{A.b.users, U.idx_own, B, A.user.id.rows};
         st.seg[st.count++] = StageSeg{A.b.pos_items, I.idx_own, B, A.item.id.rows};
-        st.seg[st.count++] = StageSeg{neg_src, neg_rows, B * N, A.item.id.rows};
+        if (N > 0) st.seg[st.count++] = StageSeg{neg_src, neg_rows, B * N, A.item.id.rows};
         if ((rc = launch_stage_rows(st, s))) return rc;
     }
     U.idx = U.fidx = U.idx_own;
@@ -2420,9 +2444,25 @@ int eval_loss(const ttamm_step_args& A, float* logits_out, hipStream_t s) {
     sa.partials = ws.partials;
     sa.blocks = ws.blocks;
     sa.logits = logits_out;
+    if (in_batch) {
+        InBatchLossArgs ib{};
+        ib.U = U.aug, ib.ldu = D, ib.B = B, ib.P = I.aug, ib.ldp = D, ib.Bc = B, ib.D = D;
+        ib.row_base = 0;
+        ib.loss_part = ws.ib_partials;
+        if ((rc = launch_inbatch_loss(ib, s))) return rc;
+        sa.skip_pos = 1;
+        sa.logits = nullptr;  // S is never stored
+        if (N > 0 && (rc = launch_score_eval(sa, s))) return rc;
+        return launch_eval_loss_inbatch_finalize(ws.partials, N > 0 ? ws.blocks : 0, ws.ib_partials, ws.ib_blocks,
+                                                 B * (B + (int64_t)N), B, A.loss_out, A.loss_accum, A.status, s);
+    }
     if ((rc = launch_score_eval(sa, s))) return rc;
     return launch_eval_loss_finalize(ws.partials, ws.blocks, B * (1 + (int64_t)N), B, A.loss_out, A.loss_accum, A.status, s);
 }
+
+int eval_loss(const ttamm_step_args& A, float* logits_out, hipStream_t s) { return eval_loss_run(A, logits_out, false, s); }
+
+int eval_loss_inbatch(const ttamm_step_args& A, hipStream_t s) { return eval_loss_run(A, nullptr, true, s); }
 
 
 // ---- training-mode tower forward / backward (module-level autograd) ------------------------

@@ -14,7 +14,7 @@ from .encoders import (
     build_id_embedding,
     build_tower_encoder,
 )
-from .inbatch import inbatch_bce
+from .inbatch import inbatch_bce, inbatch_bce_loss
 from .metrics import RankingMetrics, compute_ranking_metrics, evaluate_metrics, ranking_metrics
 from .retrieval import encode_item_embeddings, evaluate_model, prepare_faiss_resources
 from .samplers import PositivesCSR, sample_negative_items
@@ -50,6 +50,7 @@ __all__ = [
     "evaluate_metrics",
     "evaluate_model",
     "inbatch_bce",
+    "inbatch_bce_loss",
     "load_features",
     "load_interactions",
     "prepare_faiss_resources",

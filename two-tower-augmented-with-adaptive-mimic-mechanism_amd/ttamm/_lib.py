@@ -185,7 +185,7 @@ class StepArgs(ctypes.Structure):
     ]
 
 
-ABI_VERSION = 27  # ttamm.h TTAMM_ABI_VERSION
+ABI_VERSION = 28  # ttamm.h TTAMM_ABI_VERSION
 G0_EXACT = 0  # ttamm.h TTAMM_G0_EXACT
 DENSE_ADAM = 0  # ttamm.h TTAMM_DENSE_ADAM
 DENSE_SGD = 1  # ttamm.h TTAMM_DENSE_SGD
@@ -218,6 +218,8 @@ SIGNATURES = {
     "ttamm_train_step": (ctypes.c_int, [ctypes.POINTER(StepArgs), c_vp]),
     "ttamm_eval_loss_workspace_size": (ctypes.c_size_t, [ctypes.POINTER(StepArgs)]),
     "ttamm_eval_loss": (ctypes.c_int, [ctypes.POINTER(StepArgs), c_vp, c_vp]),
+    "ttamm_eval_loss_inbatch_workspace_size": (ctypes.c_size_t, [ctypes.POINTER(StepArgs)]),
+    "ttamm_eval_loss_inbatch": (ctypes.c_int, [ctypes.POINTER(StepArgs), c_vp]),
     "ttamm_dense_grad_floats": (c_i64, [ctypes.POINTER(StepArgs)]),
     "ttamm_exchange_compact_supported": (ctypes.c_int, [ctypes.POINTER(StepArgs)]),
     "ttamm_adam_history_entry_bytes": (ctypes.c_size_t, []),
@@ -293,6 +295,11 @@ SIGNATURES = {
         ctypes.c_int,
         [c_vp, c_i64, c_i64, c_vp, c_i64, c_i64, c_i32, c_i64, ctypes.c_float, c_vp, c_i64, c_vp, c_i64, c_vp, c_vp,
          ctypes.c_size_t, c_vp],
+    ),
+    "ttamm_inbatch_loss_workspace_size": (ctypes.c_size_t, [c_i64, c_i64, c_i32]),
+    "ttamm_inbatch_bce_loss": (
+        ctypes.c_int,
+        [c_vp, c_i64, c_i64, c_vp, c_i64, c_i64, c_i32, c_i64, c_vp, c_vp, ctypes.c_size_t, c_vp],
     ),
 }
 

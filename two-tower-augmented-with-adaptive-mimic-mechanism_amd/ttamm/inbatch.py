@@ -4,7 +4,8 @@ The reference scores sampled negatives only (training.py:770-798); the in-batch 
 ttamm's own (oracle/cpu_reference.py train_step(in_batch=True)): every user is scored against
 every positive of the (global) batch, label 1 on its own positive.  ``inbatch_bce`` runs the
 fused kernel the training step uses (libttamm ``ttamm_inbatch_bce``, inbatch_x_kernel on
-split-bf16 MFMA; nothing batch x n_positives is stored)."""
+split-bf16 MFMA; nothing batch x n_positives is stored); ``inbatch_bce_loss`` runs its forward
+third alone (``ttamm_inbatch_bce_loss``, inbatch_loss_kernel): the BCE sum without gradients."""
 
 from __future__ import annotations
 
@@ -13,22 +14,27 @@ import torch
 from . import _lib
 
 
-def inbatch_bce(users: torch.Tensor, positives: torch.Tensor, *, row_base: int = 0,
-                inv_count: float | None = None) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
-    """S = users @ positives.T with Y(b, row_base + b) = 1.  Returns (the BCE-with-logits sum over
-    S as a float64 device scalar, dL/dusers, dL/dpositives) for L = inv_count * that sum
-    (inv_count default 1 / S.numel(), the BCE mean)."""
+def _check_rows(users: torch.Tensor, positives: torch.Tensor, row_base: int) -> tuple[torch.Tensor, torch.Tensor]:
+    """The argument checks of both ops: contiguous float32 users [B, D] and positives [Bc, D] on
+    the device, every user's own positive inside ``positives``."""
     _lib.require_rocm(users, "inbatch_bce")
     if users.dim() != 2 or positives.dim() != 2 or users.shape[1] != positives.shape[1]:
         raise ValueError("inbatch_bce: users [B, D] and positives [Bc, D] with one D")
     if users.dtype != torch.float32 or positives.dtype != torch.float32:
         raise ValueError("inbatch_bce: float32 rows")
+    if not 0 <= row_base or row_base + users.shape[0] > positives.shape[0]:
+        raise ValueError("inbatch_bce: every user's own positive must lie in positives (row_base + B <= Bc)")
+    return users.contiguous(), positives.contiguous()
+
+
+def inbatch_bce(users: torch.Tensor, positives: torch.Tensor, *, row_base: int = 0,
+                inv_count: float | None = None) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """S = users @ positives.T with Y(b, row_base + b) = 1.  Returns (the BCE-with-logits sum over
+    S as a float64 device scalar, dL/dusers, dL/dpositives) for L = inv_count * that sum
+    (inv_count default 1 / S.numel(), the BCE mean)."""
+    users, positives = _check_rows(users, positives, row_base)
     B, D = users.shape
     Bc = positives.shape[0]
-    if not 0 <= row_base or row_base + B > Bc:
-        raise ValueError("inbatch_bce: every user's own positive must lie in positives (row_base + B <= Bc)")
-    users = users.contiguous()
-    positives = positives.contiguous()
     if inv_count is None:
         inv_count = 1.0 / float(B * Bc)
     lib = _lib.load()
@@ -42,3 +48,21 @@ def inbatch_bce(users: torch.Tensor, positives: torch.Tensor, *, row_base: int =
                                      D, d_pos.data_ptr(), D, loss.data_ptr(), ws.data_ptr(), ws.numel(),
                                      _lib.stream_handle(dev)))
     return loss, d_users, d_pos
+
+
+def inbatch_bce_loss(users: torch.Tensor, positives: torch.Tensor, *, row_base: int = 0) -> torch.Tensor:
+    """The BCE-with-logits sum over S = users @ positives.T with Y(b, row_base + b) = 1, as a
+    float64 device scalar: ``inbatch_bce(...)[0]`` without the gradients (libttamm
+    ``ttamm_inbatch_bce_loss``, the forward-only inbatch_loss_kernel; the validation loss of
+    in-batch mode).  Same argument checks as ``inbatch_bce``."""
+    users, positives = _check_rows(users, positives, row_base)
+    B, D = users.shape
+    Bc = positives.shape[0]
+    lib = _lib.load()
+    dev = users.device
+    loss = torch.empty((), dtype=torch.float64, device=dev)
+    ws = torch.empty(max(int(lib.ttamm_inbatch_loss_workspace_size(B, Bc, D)), 4), dtype=torch.uint8, device=dev)
+    _lib.check(lib.ttamm_inbatch_bce_loss(users.data_ptr(), B, users.stride(0), positives.data_ptr(), Bc,
+                                          positives.stride(0), D, int(row_base), loss.data_ptr(), ws.data_ptr(),
+                                          ws.numel(), _lib.stream_handle(dev)))
+    return loss

@@ -718,7 +718,12 @@ class FusedEvalLoss:
     (``ttamm_eval_loss``) for one model: eval-mode towers, mimic augment, dot-product scores and
     the BCE mean, with the negatives drawn on the device.  No optimizer is involved and no
     ``.grad`` is touched.  The tables are read as they are: after training with deferred AdamW,
-    call ``FusedTrainStep.finish()`` (it flushes them) before the first ``step`` here."""
+    call ``FusedTrainStep.finish()`` (it flushes them) before the first ``step`` here.
+
+    ``in_batch_negatives=True`` (ttamm's in-batch mode, not reference behaviour) makes every batch
+    one ``ttamm_eval_loss_inbatch`` call: the BCE mean over the [B, B] logits users x positives
+    (label 1 on the diagonal, never stored) and the ``negatives_per_positive >= 0`` sampled
+    negatives, the objective ``FusedTrainStep(in_batch_negatives=True)`` trains on."""
 
     def __init__(
         self,
@@ -731,14 +736,18 @@ class FusedEvalLoss:
         max_batch: int,
         seed: int | None = None,
         num_items: int | None = None,
+        in_batch_negatives: bool = False,
     ) -> None:
-        if negatives_per_positive <= 0:
+        self.in_batch = bool(in_batch_negatives)
+        if negatives_per_positive < 0 or (negatives_per_positive == 0 and not self.in_batch):
             raise ValueError("num_negatives must be greater than zero.")
         self.model = model
         self.num_neg = int(negatives_per_positive)
         ue, ie = model.user_encoder, model.item_encoder
         if not isinstance(ue, TowerEncoder) or not isinstance(ie, TowerEncoder):
             raise NotImplementedError("ttamm: towers must be ttamm.encoders.TowerEncoder")
+        if self.in_batch and (ue.output_dim % 4 != 0 or ue.output_dim > 128):
+            raise ValueError("in-batch negatives: embedding dim must be a multiple of 4, <= 128")
         self.device = ue.embedding.weight.device
         _lib.require_rocm(ue.embedding.weight, "FusedEvalLoss")
         self.num_items = int(num_items) if num_items is not None else ie.num_embeddings
@@ -768,7 +777,7 @@ class FusedEvalLoss:
         args.mimic_enabled = 1 if mimic is not None else 0
         args.b.num_neg = self.num_neg
         self.csr = None
-        if positives is not None:
+        if positives is not None and self.num_neg > 0:  # in-batch with N == 0 draws nothing
             self.csr = positives_csr(positives, device=self.device, num_users=ue.num_embeddings)
             if self.csr.max_degree >= self.num_items:
                 raise RuntimeError("a user interacted with all items; cannot sample negatives.")
@@ -787,7 +796,9 @@ class FusedEvalLoss:
             raise ValueError("ttamm: max_batch must be positive")
         args.b.batch = self.max_batch
         self.lib = _lib.load()
-        self.ws_bytes = int(self.lib.ttamm_eval_loss_workspace_size(ctypes.byref(args)))
+        size_fn = self.lib.ttamm_eval_loss_inbatch_workspace_size if self.in_batch else \
+            self.lib.ttamm_eval_loss_workspace_size
+        self.ws_bytes = int(size_fn(ctypes.byref(args)))
         self.workspace = torch.empty(self.ws_bytes, dtype=torch.uint8, device=self.device)
         args.workspace = self.workspace.data_ptr()
         args.workspace_bytes = self.ws_bytes
@@ -800,7 +811,12 @@ class FusedEvalLoss:
         """Enqueue one validation batch on the current stream (no host synchronisation).
         ``neg_items`` [B, N] injects the negatives (default: drawn on the device into
         ``neg_buffer``); ``logits_out`` (float32 [B (1 + N)]) receives the logits in the order of
-        ``torch.cat([pos_logits, neg_logits.reshape(-1)])`` (training.py:898)."""
+        ``torch.cat([pos_logits, neg_logits.reshape(-1)])`` (training.py:898).  In in-batch mode
+        (``in_batch_negatives=True``) the positives' logits are the [B, B] matrix users x positives,
+        never stored: ``logits_out`` raises ValueError; with ``negatives_per_positive == 0`` there
+        is no sampler launch and ``neg_items`` is not used."""
+        if self.in_batch and logits_out is not None:
+            raise ValueError("ttamm: logits_out is not available in in-batch mode (the [B, B] logits are never stored)")
         B = users.numel()
         if B == 0:
             return
@@ -816,7 +832,10 @@ class FusedEvalLoss:
         a.b.users = users.data_ptr()
         a.b.pos_items = pos_items.data_ptr()
         a.b.batch = B
-        if neg_items is not None:
+        if self.num_neg == 0:
+            a.b.neg_items = None
+            a.b.sample_negatives = 0
+        elif neg_items is not None:
             if neg_items.numel() != B * self.num_neg or neg_items.dtype != torch.long:
                 raise ValueError("ttamm: negatives must be int64 [batch, negatives_per_positive]")
             _lib.require_rocm(neg_items, "eval loss")
@@ -835,7 +854,10 @@ class FusedEvalLoss:
                 raise ValueError("ttamm: logits_out must be a contiguous float32 tensor of batch * (1 + negatives) elements")
             _lib.require_rocm(logits_out, "eval loss")
             out = logits_out.data_ptr()
-        _lib.check(self.lib.ttamm_eval_loss(ctypes.byref(a), out, _lib.stream_handle(self.device)))
+        if self.in_batch:
+            _lib.check(self.lib.ttamm_eval_loss_inbatch(ctypes.byref(a), _lib.stream_handle(self.device)))
+        else:
+            _lib.check(self.lib.ttamm_eval_loss(ctypes.byref(a), out, _lib.stream_handle(self.device)))
         self.batches_done += 1
 
     def finish(self) -> float:
@@ -872,6 +894,7 @@ def compute_loss(
     device: torch.device,
     batch_hook: Callable[[int, torch.Tensor, torch.Tensor], Any] | None = None,
     seed: int | None = None,
+    in_batch_negatives: bool = False,
 ) -> float:
     """Drop-in for ``_compute_loss`` (training.py:836-914) executed on the MI355X: the model is put
     (and left) in eval mode, every batch is one ``ttamm_eval_loss`` call with no host
@@ -880,7 +903,14 @@ def compute_loss(
 
     ``batch_hook(step, users, pos)`` has ``train_one_epoch``'s signature: its first result, if not
     None, is the batch's negatives [B, N] (instead of the on-device sampler); a second element is
-    ignored.  ``seed`` keys the sampler's Philox stream (default: drawn from torch's generator)."""
+    ignored.  ``seed`` keys the sampler's Philox stream (default: drawn from torch's generator).
+
+    ``in_batch_negatives=True`` validates on the in-batch objective that
+    ``train_one_epoch(in_batch_negatives=True)`` trains on (ttamm's own, not reference behaviour):
+    every batch is one ``ttamm_eval_loss_inbatch`` call, the BCE mean over the [B, B] in-batch
+    logits and the ``negatives_per_positive >= 0`` sampled negatives.  With
+    ``negatives_per_positive == 0`` a hook's negatives are ignored and ``user_positive_items`` may
+    be empty or None."""
     model.eval()
     if not isinstance(criterion, nn.BCEWithLogitsLoss) or criterion.reduction != "mean" or \
             criterion.weight is not None or criterion.pos_weight is not None:
@@ -898,12 +928,14 @@ def compute_loss(
             engine = FusedEvalLoss(
                 model, negatives_per_positive=negatives_per_positive, positives=user_positive_items,
                 user_features=user_features, item_features=item_features,
-                max_batch=max(int(size), users.numel()), seed=seed,
+                max_batch=max(int(size), users.numel()), seed=seed, in_batch_negatives=in_batch_negatives,
             )
         neg = None
         if batch_hook is not None:
             res = batch_hook(step, users_in, pos_in)
             neg = res[0] if isinstance(res, (tuple, list)) else res
+            if negatives_per_positive == 0:
+                neg = None
             if neg is not None:
                 neg = neg.to(device, torch.long).reshape(-1)
         engine.step(users, pos, neg)  # stream-ordered: inputs are recycled safely
