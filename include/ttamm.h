@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define TTAMM_ABI_VERSION 28
+#define TTAMM_ABI_VERSION 29
 
 #define TTAMM_OK 0
 #define TTAMM_E_INVALID 1 /* bad shape / config / dtype  -> ValueError   */
@@ -491,6 +491,23 @@ int ttamm_retrieval_topk(const float* queries, int64_t n_queries, int64_t ldq, c
                          int64_t ldi, int32_t dim, const int64_t* blocked_offsets, const int64_t* blocked_values,
                          int32_t k, float* out_scores, int64_t* out_ids, void* workspace, size_t workspace_bytes,
                          void* stream);
+
+/* Merge of n_lists top-k lists per query into one — the cross-rank step of a row-sharded
+ * retrieval (every rank ran ttamm_retrieval_topk over its item shard; an all-to-all left the
+ * W partial lists of this rank's queries in one list-major [W, n_queries, k] buffer).  List l of
+ * query q is the k_in entries at l * list_stride + q * query_stride (strides in elements, the
+ * same layout in scores and ids); an entry with id < 0 is a hole whatever its score; a list need
+ * not be sorted.  Output rows [n_queries, k_out], contiguous: the k_out best non-hole entries,
+ * score descending, then global id ascending, where global id = id * id_stride + l (64-bit; with
+ * items dealt to ranks by id % W, id_stride = W turns a shard's local row into the item id);
+ * then -inf / -1.  n_lists = 1, id_stride = 1 re-sorts one list.  Nothing is assumed about NaN
+ * scores.  One wave per query sorts 512 entries in registers and folds longer inputs in by
+ * rounds; the split is a function of the shapes, no atomics: same inputs, same bits.
+ * TTAMM_E_INVALID before any device work: k_in or k_out outside [1, 192], n_lists outside
+ * [1, 1024], id_stride < 1, n_queries < 0.  n_queries == 0 launches nothing. */
+int ttamm_topk_merge(const float* scores, const int64_t* ids, int32_t n_lists, int64_t n_queries, int32_t k_in,
+                     int64_t list_stride, int64_t query_stride, int32_t id_stride, int32_t k_out, float* out_scores,
+                     int64_t* out_ids, void* stream);
 
 /* The no-FAISS branch of _evaluate_model, _retrieve_with_sampling (training.py:974-1009): query q
  * scores its candidate list — items rows cand_rows[cand_offsets[q] .. cand_offsets[q+1]), at most

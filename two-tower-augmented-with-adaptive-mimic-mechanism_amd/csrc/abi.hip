@@ -87,6 +87,14 @@ TTAMM_API int ttamm_retrieval_topk(const float* queries, int64_t n_queries, int6
                                  out_scores, out_ids, workspace, workspace_bytes, (hipStream_t)stream);
 }
 
+TTAMM_API int ttamm_topk_merge(const float* scores, const int64_t* ids, int32_t n_lists, int64_t n_queries,
+                               int32_t k_in, int64_t list_stride, int64_t query_stride, int32_t id_stride,
+                               int32_t k_out, float* out_scores, int64_t* out_ids, void* stream) {
+    g_last_error.clear();
+    return launch_topk_merge(scores, ids, n_lists, n_queries, k_in, list_stride, query_stride, id_stride, k_out,
+                             out_scores, out_ids, (hipStream_t)stream);
+}
+
 TTAMM_API int ttamm_candidate_topk(const float* queries, int64_t n_queries, int64_t ldq, const float* items,
                                    int64_t n_items, int64_t ldi, int32_t dim, const int64_t* cand_offsets,
                                    const int64_t* cand_rows, int32_t max_candidates, int32_t cosine, int32_t k,

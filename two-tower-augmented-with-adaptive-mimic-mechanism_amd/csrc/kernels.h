@@ -454,6 +454,9 @@ int launch_candidate_topk(const float* Q, int64_t nq, int64_t ldq, const float* 
 int launch_retrieval_topk(const float* Q, int64_t nq, int64_t ldq, const float* X, int64_t ni, int64_t ldx, int dim,
                           const int64_t* boff, const int64_t* bval, int k, float* out_s, int64_t* out_i, void* ws,
                           size_t ws_bytes, hipStream_t s);
+// merge of n_lists top-k lists per query into one (ttamm.h ttamm_topk_merge)
+int launch_topk_merge(const float* scores, const int64_t* ids, int n_lists, int64_t nq, int k_in, int64_t list_stride,
+                      int64_t query_stride, int id_stride, int k_out, float* out_s, int64_t* out_i, hipStream_t s);
 
 // ------------------------------------------------------------------------------------
 // Ranking metrics of predicted id rows against ground-truth CSR segments (metrics.hip)

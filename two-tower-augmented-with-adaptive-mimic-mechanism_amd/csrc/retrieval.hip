@@ -15,6 +15,8 @@
 // D <= 128 runs the same scheme on split-bf16 MFMA (retrieval_x_kernel: fp32-level scores at
 // 2.6x the fp32 MFMA rate; TTAMM_RETRIEVAL_FP32=1 keeps the fp32 kernel for comparison).
 // Pass 2 (retrieval_merge_kernel): one wave per query merges the partitions' top-k lists.
+// topk_merge_kernel (ttamm_topk_merge) is the cross-rank merge of a row-sharded search: the
+// per-shard lists of a query, 64-bit global ids, any number of candidates in 512-slot rounds.
 #include <cfloat>
 #include <cstdlib>
 #include <cstring>
@@ -37,9 +39,14 @@ __device__ __forceinline__ bool better(float sa, int ia, float sb, int ib) {
     return sa > sb || (sa == sb && (unsigned)ia < (unsigned)ib);
 }
 
+// 64-bit ids (ttamm_topk_merge's global ids, all >= 0; holes carry INT64_MAX)
+__device__ __forceinline__ bool better(float sa, int64_t ia, float sb, int64_t ib) {
+    return sa > sb || (sa == sb && ia < ib);
+}
+
 // Sort the 64*J (score, id) pairs of a wave — element e = lane*J + j — best first.
-template <int J>
-__device__ void wave_bitonic_sort(float (&s)[J], int (&id)[J]) {
+template <int J, typename I>
+__device__ void wave_bitonic_sort(float (&s)[J], I (&id)[J]) {
     const int lane = threadIdx.x & 63;
     constexpr int N = 64 * J;
 #pragma unroll
@@ -52,7 +59,7 @@ __device__ void wave_bitonic_sort(float (&s)[J], int (&id)[J]) {
                 for (int j = 0; j < J; ++j) {
                     const int e = lane * J + j;
                     const float ps = __shfl_xor(s[j], ls, 64);
-                    const int pi = __shfl_xor(id[j], ls, 64);
+                    const I pi = __shfl_xor(id[j], ls, 64);
                     const bool dir = (e & size) == 0;       // block sorted best-first
                     const bool lower = (e & stride) == 0;
                     const bool mine_better = better(s[j], id[j], ps, pi);
@@ -70,7 +77,7 @@ __device__ void wave_bitonic_sort(float (&s)[J], int (&id)[J]) {
                     const int k = j | stride;
                     if (better(s[k], id[k], s[j], id[j]) == dir) {
                         const float ts = s[j];
-                        const int ti = id[j];
+                        const I ti = id[j];
                         s[j] = s[k];
                         id[j] = id[k];
                         s[k] = ts;
@@ -152,7 +159,7 @@ __device__ int compact_core(float* __restrict__ bs, int* __restrict__ bi, int q,
         }
         n = kept;
     }
-    wave_bitonic_sort<4>(s, id);
+    wave_bitonic_sort(s, id);
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
         const int e = lane * 4 + j;
@@ -516,7 +523,7 @@ __global__ __launch_bounds__(64) void retrieval_merge_kernel(RetrievalArgs A, fl
         id[j] = e < n ? A.part_i[q * n + e] : -1;
         if (id[j] < 0) s[j] = -INFINITY;  // empty slots sort last
     }
-    wave_bitonic_sort<kMergeJ>(s, id);
+    wave_bitonic_sort(s, id);
 #pragma unroll
     for (int j = 0; j < kMergeJ; ++j) {
         const int e = lane * kMergeJ + j;
@@ -524,6 +531,66 @@ __global__ __launch_bounds__(64) void retrieval_merge_kernel(RetrievalArgs A, fl
             const bool ok = id[j] >= 0;
             out_s[q * A.k + e] = ok ? s[j] : -INFINITY;
             out_i[q * A.k + e] = ok ? (int64_t)id[j] : -1;
+        }
+    }
+}
+
+// ttamm_topk_merge: the cross-rank merge of per-shard top-k lists (one wave per query, four
+// queries per block).  Candidate c of a query is entry c % k_in of list c / k_in; its key is
+// (score, global id = id * id_stride + list) in 64 bits, a hole (id < 0) is (-inf, INT64_MAX),
+// which sorts after every real entry whatever its score.  The wave sorts kMergeSlots = 512 keys
+// in registers; more candidates than that are folded in by rounds: after a sort the best k_out
+// stay where they are (elements [0, k_out)) and the other 512 - k_out elements are reloaded with
+// the next candidates.  Which candidate lands in which round and slot depends on the shapes
+// only, and the sort is a total order (distinct global ids), so the result is a function of the
+// inputs alone.
+constexpr int kMergeSlots = 64 * kMergeJ;
+constexpr int kMergeMaxK = kRCap - kRI;   // 192, the k limit of ttamm_retrieval_topk
+constexpr int kMergeMaxLists = 1024;
+
+__global__ __launch_bounds__(256) void topk_merge_kernel(const float* __restrict__ scores,
+                                                         const int64_t* __restrict__ ids, int n_lists, int64_t nq,
+                                                         int k_in, int64_t list_stride, int64_t query_stride,
+                                                         int id_stride, int k_out, float* __restrict__ out_s,
+                                                         int64_t* __restrict__ out_i) {
+    const int lane = threadIdx.x & 63;
+    const int64_t q = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (q >= nq) return;  // whole waves leave together: the shuffles below stay converged
+    const int n = n_lists * k_in;  // <= 1024 * 192
+    const float* qs = scores + q * query_stride;
+    const int64_t* qi = ids + q * query_stride;
+    float s[kMergeJ];
+    int64_t g[kMergeJ];
+    int keep = 0;  // elements [0, keep) hold the running best
+    for (int base = 0; base < n; base += kMergeSlots - keep, keep = k_out) {  // n >= 1
+#pragma unroll
+        for (int j = 0; j < kMergeJ; ++j) {
+            const int e = lane * kMergeJ + j;
+            if (e < keep) continue;
+            const int c = base + (e - keep);
+            float sc = -INFINITY;
+            int64_t gid = INT64_MAX;
+            if (c < n) {
+                const int l = c / k_in, p = c - l * k_in;
+                const int64_t off = (int64_t)l * list_stride + p;
+                const int64_t id = qi[off];
+                if (id >= 0) {
+                    sc = qs[off];
+                    gid = id * (int64_t)id_stride + l;
+                }
+            }
+            s[j] = sc;
+            g[j] = gid;
+        }
+        wave_bitonic_sort(s, g);
+    }
+#pragma unroll
+    for (int j = 0; j < kMergeJ; ++j) {
+        const int e = lane * kMergeJ + j;
+        if (e < k_out) {
+            const bool ok = g[j] != INT64_MAX;
+            out_s[q * k_out + e] = ok ? s[j] : -INFINITY;
+            out_i[q * k_out + e] = ok ? g[j] : int64_t(-1);
         }
     }
 }
@@ -729,6 +796,22 @@ int launch_normalize_rows(float* x, int64_t n, int dim, int64_t ld, hipStream_t 
     if (n == 0) return TTAMM_OK;
     TTAMM_REQUIRE(x != nullptr, "normalize_rows: null rows");
     hipLaunchKernelGGL(normalize_rows_kernel, dim3((unsigned)ceil_div(n, 4)), dim3(256), 0, s, x, n, dim, ld);
+    TTAMM_LAUNCH_CHECK();
+    return TTAMM_OK;
+}
+
+int launch_topk_merge(const float* scores, const int64_t* ids, int n_lists, int64_t nq, int k_in, int64_t list_stride,
+                      int64_t query_stride, int id_stride, int k_out, float* out_s, int64_t* out_i, hipStream_t s) {
+    TTAMM_REQUIRE(k_in >= 1 && k_in <= kMergeMaxK && k_out >= 1 && k_out <= kMergeMaxK,
+                  "topk_merge: k_in and k_out must be in [1, 192]");
+    TTAMM_REQUIRE(n_lists >= 1 && n_lists <= kMergeMaxLists, "topk_merge: n_lists must be in [1, 1024]");
+    TTAMM_REQUIRE(id_stride >= 1, "topk_merge: id_stride must be >= 1");
+    TTAMM_REQUIRE(nq >= 0 && nq < (int64_t(1) << 32), "topk_merge: bad query count");
+    TTAMM_REQUIRE(list_stride >= 0 && query_stride >= 0, "topk_merge: negative strides");
+    if (nq == 0) return TTAMM_OK;
+    TTAMM_REQUIRE(scores && ids && out_s && out_i, "topk_merge: null pointer");
+    hipLaunchKernelGGL(topk_merge_kernel, dim3((unsigned)ceil_div(nq, 4)), dim3(256), 0, s, scores, ids, n_lists, nq, k_in,
+                       list_stride, query_stride, id_stride, k_out, out_s, out_i);
     TTAMM_LAUNCH_CHECK();
     return TTAMM_OK;
 }

@@ -16,7 +16,7 @@ from .encoders import (
 )
 from .inbatch import inbatch_bce, inbatch_bce_loss
 from .metrics import RankingMetrics, compute_ranking_metrics, evaluate_metrics, ranking_metrics
-from .retrieval import encode_item_embeddings, evaluate_model, prepare_faiss_resources
+from .retrieval import encode_item_embeddings, evaluate_model, prepare_faiss_resources, topk_merge
 from .samplers import PositivesCSR, sample_negative_items
 from .training import (
     DotProductSimilarity,
@@ -58,5 +58,6 @@ __all__ = [
     "sample_negative_items",
     "save_features",
     "save_interactions",
+    "topk_merge",
     "train_one_epoch",
 ]

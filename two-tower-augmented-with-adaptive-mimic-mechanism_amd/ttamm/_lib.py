@@ -185,7 +185,7 @@ class StepArgs(ctypes.Structure):
     ]
 
 
-ABI_VERSION = 28  # ttamm.h TTAMM_ABI_VERSION
+ABI_VERSION = 29  # ttamm.h TTAMM_ABI_VERSION
 G0_EXACT = 0  # ttamm.h TTAMM_G0_EXACT
 DENSE_ADAM = 0  # ttamm.h TTAMM_DENSE_ADAM
 DENSE_SGD = 1  # ttamm.h TTAMM_DENSE_SGD
@@ -241,6 +241,10 @@ SIGNATURES = {
     "ttamm_retrieval_topk": (
         ctypes.c_int,
         [c_vp, c_i64, c_i64, c_vp, c_i64, c_i64, c_i32, c_vp, c_vp, c_i32, c_vp, c_vp, c_vp, ctypes.c_size_t, c_vp],
+    ),
+    "ttamm_topk_merge": (
+        ctypes.c_int,
+        [c_vp, c_vp, c_i32, c_i64, c_i32, c_i64, c_i64, c_i32, c_i32, c_vp, c_vp, c_vp],
     ),
     "ttamm_ranking_metrics_workspace_size": (ctypes.c_size_t, [c_i64, c_i32]),
     "ttamm_ranking_metrics": (

@@ -157,6 +157,31 @@ def retrieve_topk(queries: torch.Tensor, items: torch.Tensor, k: int, *,
     return scores, ids
 
 
+def topk_merge(scores: torch.Tensor, ids: torch.Tensor, k: int, *, id_stride: int = 1
+               ) -> tuple[torch.Tensor, torch.Tensor]:
+    """``ttamm_topk_merge``: (scores [nq, k], ids [nq, k]) from ``n_lists`` lists per query,
+    ``scores`` float32 and ``ids`` int64 device tensors [n_lists, nq, k_in] of one layout (any
+    list / query strides, unit stride along k_in).  Per query the k best entries with id >= 0, by
+    score descending then global id = id * id_stride + list ascending; -inf / -1 past them.  The
+    lists need not be sorted; k, k_in <= 192, n_lists <= 1024."""
+    _lib.require_rocm(scores, "topk_merge")
+    if scores.dtype != torch.float32 or ids.dtype != torch.long:
+        raise ValueError("ttamm topk_merge: float32 scores and int64 ids are required")
+    if scores.dim() != 3 or scores.shape != ids.shape or ids.device != scores.device:
+        raise ValueError("ttamm topk_merge: scores and ids must be [n_lists, n_queries, k_in] on one device")
+    n_lists, nq, k_in = scores.shape
+    if nq and k_in and n_lists and (scores.stride() != ids.stride() or scores.stride(2) != 1):
+        raise ValueError("ttamm topk_merge: scores and ids must share their strides, with unit stride along k_in")
+    out_s = torch.empty((nq, k), dtype=torch.float32, device=scores.device)
+    out_i = torch.empty((nq, k), dtype=torch.long, device=scores.device)
+    live = nq > 0 and k_in > 0 and n_lists > 0
+    _lib.check(_lib.load().ttamm_topk_merge(
+        scores.data_ptr() if live else None, ids.data_ptr() if live else None, n_lists, nq, k_in,
+        scores.stride(0) if live else 0, scores.stride(1) if live else 0, id_stride, k, out_s.data_ptr(),
+        out_i.data_ptr(), _lib.stream_handle(scores.device)))
+    return out_s, out_i
+
+
 def prepare_faiss_resources(model, *, num_items: int, item_features: torch.Tensor | None, device: torch.device,
                             similarity_module: nn.Module | None = None, batch_size: int = 262_144,
                             retain_embeddings: bool = False) -> dict[str, Any] | None:

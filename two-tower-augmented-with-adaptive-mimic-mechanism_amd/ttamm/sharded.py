@@ -32,6 +32,9 @@ global batch.  Every rank sweeps AdamW(g=0) over its own table shards only.
 The step is written as an SPMD program that yields a request at each collective.
 ``TorchComm`` serves the requests with torch.distributed (RCCL on ROCm, gloo on CPU);
 ``run_loopback`` runs W programs in one process in lock step (the single-GPU parity test).
+
+The evaluation of a sharded model (exact top-k over the item shards, ranking metrics) is written
+the same way in ``sharded_eval.py``; its entry points are re-exported at the end of this module.
 """
 
 from __future__ import annotations
@@ -850,3 +853,9 @@ def train_one_epoch_sharded(engine: ShardedTrainStep, batches: Any, comm: Callab
         raise RuntimeError("ttamm: train_one_epoch_sharded needs comm= (e.g. TorchComm())")
     runner = comm.run if hasattr(comm, "run") else comm
     return runner(epoch_program(engine, batches))
+
+
+# the row-sharded evaluation (exact top-k + ranking metrics) lives in sharded_eval.py; its entry
+# points are part of this module's interface
+from .sharded_eval import (evaluate_metrics_program, evaluate_metrics_sharded, retrieve_topk_program,  # noqa: E402,F401
+                           route_blocked)
