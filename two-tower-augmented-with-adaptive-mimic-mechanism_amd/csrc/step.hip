@@ -21,73 +21,11 @@
 #include <cstring>
 #include <vector>
 
-#include "kernels.h"
+#include "tower.h"
 
 namespace ttamm {
 
 namespace {
-
-enum Role { ROLE_USER = 0, ROLE_ITEM = 1 };
-
-struct TowerWs {
-    int role = ROLE_USER;
-    int64_t R = 0;
-    const int64_t* idx = nullptr;   // ID / mimic table rows
-    const int64_t* fidx = nullptr;  // feature rows (null: row r)
-    int64_t* idx_own = nullptr;     // staged (range-checked) rows: users / 1-process items [pos; neg] /
-                                    // sharded owner's requested local item rows
-    // dropout stream key of row r (see GemmProblem::row_key)
-    const int64_t* row_key = nullptr;
-    int64_t key_base0 = 0, key_base1 = 0, key_split = 0;
-    // ID-table max_norm: per-row claim marks (persistent, zero once) and this call's tag base
-    int32_t* renorm_mark = nullptr;
-    int32_t renorm_tag = 0;
-    int64_t renorm_split = 0;  // item tower: positives [0, split) are one lookup, negatives the next
-    int64_t renorm_key_split = 0;  // sharded owner: requests with row_key < this (positives) are one lookup
-    float* hid[TTAMM_MAX_LINEAR] = {};
-    float* dhid[TTAMM_MAX_LINEAR] = {};
-    // non-ReLU activations: each hidden layer's pre-activation, its drawn keep bytes (dropout
-    // without an injected mask), and the keep bytes the backward reads (injected or drawn)
-    float* pre[TTAMM_MAX_LINEAR] = {};
-    uint8_t* mask[TTAMM_MAX_LINEAR] = {};
-    const uint8_t* keep[TTAMM_MAX_LINEAR] = {};
-    float* ef = nullptr;    // gated: [R, 2D] = [e | f]
-    float* e = nullptr;     // non-gated: [R, D]
-    float* f = nullptr;     // sum fusion: [R, D]
-    float* z = nullptr;     // gate hidden [R, Hg]
-    float* dz = nullptr;
-    float* g = nullptr;
-    float* t = nullptr;     // [R, t_ld] (a alongside at the same stride)
-    float* a = nullptr;
-    int64_t t_ld = 0;
-    float* aug = nullptr;   // [R, D] or null (sharded item owner)
-    const float* dT = nullptr;  // [R, dT_ld]
-    float* dT_own = nullptr;
-    int64_t dT_ld = 0;
-    const float* dA = nullptr;  // mimic-table grad rows (user: all rows; item: positives or all)
-    float* dA_own = nullptr;
-    int64_t dA_ld = 0;
-    int64_t dA_split = 0;       // rows < dA_split read dA, the rest read dT
-    const int64_t* xu = nullptr;  // sharded owner, compact exchange rows: row units (GateTower::xu)
-    float* dq = nullptr;
-    float* dEF = nullptr;  // [R, 2D]
-    float* gw[TTAMM_MAX_LINEAR] = {};
-    float* gb[TTAMM_MAX_LINEAR] = {};
-    float* ggw[2] = {};
-    float* ggb[2] = {};
-    float* slab[TTAMM_MAX_LINEAR + 2] = {};
-    CoalesceWs co{};
-    CatchupList cl{};  // deferred AdamW: the batch's rows to bring current, grouped by lag
-    float* side_id = nullptr;
-    float* side_mimic = nullptr;
-    float* piece_e = nullptr;
-    float* piece_a = nullptr;
-    float* wpad = nullptr;  // first feature layer weight, in_features padded to a multiple of 4
-    uint16_t* w16 = nullptr;  // bf16 towers with bf16 feature rows: the weight rounded, padded to % 8
-    uint16_t* gw16 = nullptr;  // bf16 gated towers (D == Hg in {128, 256}): the fused gate's weight images
-    bool gw16_ready = false;   // formed by this call's forward (the weights do not change before its backward)
-    int wgrad_rps[kWgradClasses] = {512, 512, 512, 512};  // split-K rows of the weight gradients, per tile class
-};
 
 struct StepWs {
     TowerWs user, item;
@@ -119,143 +57,13 @@ bool cal_enabled(const ttamm_step_args& A) {
     return A.item_categories != nullptr && A.hp.lambda_category_alignment > 0.0;
 }
 
-int tower_in_dim(const ttamm_tower& T, int l) { return l == 0 ? T.feat_dim : T.linear[l - 1].out_features; }
-inline int round4(int x) { return (x + 3) / 4 * 4; }
-inline int round8(int x) { return (x + 7) / 8 * 8; }
-// the first feature layer's forward on bf16 operands in memory (ttamm_tower.features_bf16)
-bool uses_w16(const ttamm_tower& T) {
-    return T.matmul_bf16 && T.features_bf16 != nullptr && T.fusion != TTAMM_FUSION_IDENTITY && T.n_linear > 0;
-}
-// gated and concat towers keep [e | f] rows (the gate's / projection's input) and their gradient
-bool uses_ef(const ttamm_tower& T) { return T.fusion == TTAMM_FUSION_GATED || T.fusion == TTAMM_FUSION_CONCAT; }
-// Linear layers after the feature encoder: the gate's two, or the concat projection
-int fusion_linears(const ttamm_tower& T) {
-    return T.fusion == TTAMM_FUSION_GATED ? 2 : T.fusion == TTAMM_FUSION_CONCAT ? 1 : 0;
-}
-// widths of a tower: the ID rows (Did), the feature encoder's output (Fo), the [e | f] rows of
-// gated / concat fusion (Did + Fo) and the tower output (concat: the projection's output_dim,
-// encoders.py:211-217; otherwise Did).  Everything downstream of the tower (scores, mimic
-// tables, the exchange rows) is output-wide; only concat lets the output differ from Did.
-int fo_dim(const ttamm_tower& T) { return T.n_linear ? T.linear[T.n_linear - 1].out_features : T.feat_dim; }
-int efw(const ttamm_tower& T) { return T.id.dim + fo_dim(T); }
-int out_dim(const ttamm_tower& T) { return T.fusion == TTAMM_FUSION_CONCAT ? T.gate[0].out_features : T.id.dim; }
-bool needs_wpad(const ttamm_tower& T) {
-    return T.fusion != TTAMM_FUSION_IDENTITY && T.n_linear > 0 && T.linear[0].in_features % 4 != 0;
-}
-
-// Validate one tower against the reference's own constraints.
-int validate_tower(const ttamm_tower& T, const char* name, int D, bool training) {
-    std::string n(name);
-    TTAMM_REQUIRE(T.id.weight, n + ": embedding table missing");
-    if (training) TTAMM_REQUIRE(T.id.exp_avg && T.id.exp_avg_sq, n + ": embedding optimizer state missing");
-    TTAMM_REQUIRE(T.fusion == TTAMM_FUSION_CONCAT || T.id.dim == D, n + ": embedding dim mismatch");
-    TTAMM_REQUIRE(D % 4 == 0 && T.id.dim % 4 == 0, n + ": ttamm requires embedding_dim % 4 == 0");
-    TTAMM_REQUIRE(T.id.rows > 0, n + ": empty embedding table");
-    TTAMM_REQUIRE(T.id.rows < (int64_t(1) << 31), n + ": tables of 2^31 rows or more are not supported (int32 row keys)");
-    TTAMM_REQUIRE(T.n_linear >= 0 && T.n_linear <= TTAMM_MAX_LINEAR, n + ": too many feature-encoder layers");
-    TTAMM_REQUIRE(T.activation >= TTAMM_ACT_RELU && T.activation <= TTAMM_ACT_SELU, n + ": unsupported activation");
-    TTAMM_REQUIRE(T.fusion >= TTAMM_FUSION_IDENTITY && T.fusion <= TTAMM_FUSION_CONCAT, n + ": unsupported fusion");
-    if (T.fusion != TTAMM_FUSION_IDENTITY) {
-        TTAMM_REQUIRE(T.features != nullptr && T.feat_dim > 0, n + ": fusion needs feature rows");
-        TTAMM_REQUIRE(T.feat_ld >= T.feat_dim, n + ": feature row stride too small");
-        // the feature rows are [id.rows, feat_ld]: the weight gradient keeps their gathered row ids as int32
-        TTAMM_REQUIRE(T.id.rows < (int64_t(1) << 31), n + ": feature rows of 2^31 rows or more are not supported "
-                                                          "(the weight gradient gathers them by int32 row ids)");
-        TTAMM_REQUIRE(T.feat_ld % 4 == 0 && (uintptr_t)T.features % 16 == 0,
-                      n + ": feature rows must be 16-byte aligned (row stride % 4 == 0)");
-        if (T.features_bf16)
-            TTAMM_REQUIRE(T.matmul_bf16 && T.feat_bf16_ld % 8 == 0 && T.feat_bf16_ld >= round8(T.feat_dim) &&
-                              (uintptr_t)T.features_bf16 % 16 == 0,
-                          n + ": bf16 feature rows need matmul_bf16, 16-byte aligned rows of >= round8(F) elements");
-        if (T.features_planes)
-            TTAMM_REQUIRE(!T.matmul_bf16 && T.feat_planes_ld % 8 == 0 &&
-                              T.feat_planes_ld >= 48 * ceil_div(T.feat_dim, 16) && (uintptr_t)T.features_planes % 16 == 0,
-                          n + ": feature planes need fp32 GEMMs and 16-byte aligned rows of >= 48 ceil(F / 16) "
-                              "elements (a multiple of 8)");
-        for (int l = 0; l < T.n_linear; ++l) {
-            const ttamm_linear& L = T.linear[l];
-            TTAMM_REQUIRE(L.weight && L.bias, n + ": linear parameters missing");
-            if (training)
-                TTAMM_REQUIRE(L.weight_exp_avg && L.weight_exp_avg_sq && L.bias_exp_avg && L.bias_exp_avg_sq,
-                              n + ": linear optimizer state missing");
-            TTAMM_REQUIRE(L.in_features == tower_in_dim(T, l), n + ": feature-encoder layer shapes do not chain");
-            TTAMM_REQUIRE(L.out_features % 4 == 0, n + ": ttamm requires feature-encoder widths % 4 == 0");
-        }
-        const int fo = fo_dim(T);
-        if (T.fusion == TTAMM_FUSION_CONCAT)
-            TTAMM_REQUIRE(fo % 4 == 0, n + ": ttamm requires the feature encoder's output width % 4 == 0");
-        else
-            TTAMM_REQUIRE(fo == D, n + ": Feature encoder output dimension must match id embedding dimension for "
-                                       "'sum' or 'gated' fusion.");
-        TTAMM_REQUIRE(T.dropout >= 0.f && T.dropout < 1.f, n + ": dropout must be in [0, 1)");
-    }
-    if (T.fusion == TTAMM_FUSION_GATED) {
-        const ttamm_linear &G1 = T.gate[0], &G2 = T.gate[1];
-        TTAMM_REQUIRE(G1.weight && G1.bias && G2.weight && G2.bias, n + ": gate parameters missing");
-        if (training)
-            TTAMM_REQUIRE(G1.weight_exp_avg && G1.weight_exp_avg_sq && G1.bias_exp_avg && G1.bias_exp_avg_sq &&
-                              G2.weight_exp_avg && G2.weight_exp_avg_sq && G2.bias_exp_avg && G2.bias_exp_avg_sq,
-                          n + ": gate optimizer state missing");
-        TTAMM_REQUIRE(G1.in_features == 2 * D && G2.out_features == D && G2.in_features == G1.out_features,
-                      n + ": gate shapes do not match the embedding dimension");
-        TTAMM_REQUIRE(G1.out_features % 4 == 0, n + ": ttamm requires the gate hidden width % 4 == 0");
-    }
-    if (T.fusion == TTAMM_FUSION_CONCAT) {
-        const ttamm_linear& P = T.gate[0];
-        TTAMM_REQUIRE(P.weight && P.bias, n + ": concat projection parameters missing");
-        if (training)
-            TTAMM_REQUIRE(P.weight_exp_avg && P.weight_exp_avg_sq && P.bias_exp_avg && P.bias_exp_avg_sq,
-                          n + ": concat projection optimizer state missing");
-        TTAMM_REQUIRE(P.in_features == efw(T) && P.out_features == D,
-                      n + ": concat projection must map [e | f] (embedding dim + feature output) to the output dim");
-    }
-    return TTAMM_OK;
-}
-
 bool sharded(const ttamm_step_args& A) { return A.phase != TTAMM_PHASE_ALL; }
 // compact exchange rows (ttamm.h ttamm_step_args.exchange_counts)
 bool compact_exchange(const ttamm_step_args& A) { return sharded(A) && A.exchange_counts != nullptr; }
 int64_t global_batch(const ttamm_step_args& A) { return A.global_batch > 0 ? A.global_batch : A.b.batch; }
 
-// The replicated-weight gradient arena: per tower (user, item) the feature-encoder layers'
-// weight, bias, then the gate's, each piece padded to 64 floats (256 B).
-inline size_t pad64(size_t n) { return (n + 63) / 64 * 64; }
-size_t tower_grad_floats(const ttamm_tower& T) {
-    size_t n = 0;
-    if (T.fusion == TTAMM_FUSION_IDENTITY) return 0;
-    for (int l = 0; l < T.n_linear; ++l)
-        n += pad64((size_t)T.linear[l].out_features * T.linear[l].in_features) + pad64(T.linear[l].out_features);
-    for (int q = 0; q < fusion_linears(T); ++q)
-        n += pad64((size_t)T.gate[q].out_features * T.gate[q].in_features) + pad64(T.gate[q].out_features);
-    return n;
-}
-void carve_grads(const ttamm_tower& T, TowerWs& w, float*& cur) {
-    if (T.fusion == TTAMM_FUSION_IDENTITY) return;
-    for (int l = 0; l < T.n_linear; ++l) {
-        w.gw[l] = cur;
-        cur += pad64((size_t)T.linear[l].out_features * T.linear[l].in_features);
-        w.gb[l] = cur;
-        cur += pad64(T.linear[l].out_features);
-    }
-    for (int q = 0; q < fusion_linears(T); ++q) {
-            w.ggw[q] = cur;
-            cur += pad64((size_t)T.gate[q].out_features * T.gate[q].in_features);
-            w.ggb[q] = cur;
-            cur += pad64(T.gate[q].out_features);
-        }
-}
-
 // Workspace layout.  Deterministic in the arguments, so every phase call of a sharded step
 // finds the previous phases' activations where it left them.
-// The weight-gradient problems of one tower (tower_backward's list), for the split choice.
-int wgrad_shapes(const ttamm_tower& T, int64_t R, WgradShape* out) {
-    int n = 0;
-    if (T.fusion == TTAMM_FUSION_IDENTITY) return 0;
-    for (int l = 0; l < T.n_linear; ++l) out[n++] = WgradShape{R, T.linear[l].out_features, T.linear[l].in_features};
-    for (int q = 0; q < fusion_linears(T); ++q) out[n++] = WgradShape{R, T.gate[q].out_features, T.gate[q].in_features};
-    return n;
-}
-
 // Per-row scratch of the row grouping (CoalesceWs cnt / first / fill) comes first in the
 // workspace: its offsets depend only on the table sizes, so it stays in place (and zero between
 // calls, as launch_coalesce leaves it) whatever the batch size.  The caller zeroes the
@@ -272,17 +80,6 @@ void plan_scratch(Arena& ar, const ttamm_step_args& A, StepWs& ws) {
     // step_prologue_kernel's completion counter: its last block resets it, so it must sit at a
     // batch-size-independent offset (a short last batch must find it zero, not old activations)
     ws.prologue_done = ar.take<uint32_t>(1);
-}
-
-// the split-K slabs of a tower's weight gradients (w.wgrad_rps chosen before): the feature
-// encoder's layers, then the fusion's
-void plan_slabs(Arena& ar, const ttamm_tower& T, int64_t R, TowerWs& w) {
-    if (T.fusion == TTAMM_FUSION_IDENTITY) return;
-    for (int i = 0; i < T.n_linear + fusion_linears(T); ++i) {
-        const ttamm_linear& L = i < T.n_linear ? T.linear[i] : T.gate[i - T.n_linear];
-        w.slab[i < T.n_linear ? i : TTAMM_MAX_LINEAR + i - T.n_linear] = ar.take<float>(
-            wgrad_slab_floats((int)R, L.out_features, L.in_features, w.wgrad_rps[wgrad_class(L.out_features)]));
-    }
 }
 
 void plan_coalesce(Arena& ar, CoalesceWs& co, int64_t R) {
@@ -314,53 +111,18 @@ int plan(Arena& ar, const ttamm_step_args& A, StepWs& ws) {
     }
     // ext_io: the item tower's t / a / dT / dA live in the caller's exchange buffers
     auto tower = [&](const ttamm_tower& T, TowerWs& w, int64_t R, bool ext_io, int64_t dA_rows) {
-        w.R = R;
-        w.idx_own = ar.take<int64_t>(R);
-        for (int l = 0; l + 1 < T.n_linear; ++l) {
-            w.hid[l] = ar.take<float>((size_t)R * T.linear[l].out_features);
-            w.dhid[l] = ar.take<float>((size_t)R * T.linear[l].out_features);
-            if (T.activation != TTAMM_ACT_RELU) {
-                w.pre[l] = ar.take<float>((size_t)R * T.linear[l].out_features);
-                if (T.dropout > 0.f) w.mask[l] = ar.take<uint8_t>((size_t)R * T.linear[l].out_features);
-            }
-        }
-        const int Hg = T.fusion == TTAMM_FUSION_GATED ? T.gate[0].out_features : 0;
-        if (uses_ef(T)) {
-            w.ef = ar.take<float>((size_t)R * efw(T));
-            w.dEF = ar.take<float>((size_t)R * efw(T));
-        }
-        if (T.fusion == TTAMM_FUSION_GATED) {
-            w.z = ar.take<float>((size_t)R * Hg);
-            w.dz = ar.take<float>((size_t)R * Hg);
-            w.g = ar.take<float>((size_t)R * D);
-            w.dq = ar.take<float>((size_t)R * D);
-            const int np = T.matmul_bf16 ? 1 : 3;
-            if (gate16_supported(D, Hg, np)) w.gw16 = ar.take<uint16_t>((size_t)gate16_image_elems(D, Hg, np));
-        } else if (!uses_ef(T)) {
-            w.e = ar.take<float>((size_t)R * D);
-            if (T.fusion == TTAMM_FUSION_SUM) w.f = ar.take<float>((size_t)R * D);
-        }
-        if (!ext_io) {
-            w.t = ar.take<float>((size_t)R * D);
-            w.a = mimic ? ar.take<float>((size_t)R * D) : nullptr;
-            w.t_ld = D;
-            w.aug = ar.take<float>((size_t)R * D);
-            w.dT_own = ar.take<float>((size_t)R * D);
-            w.dT = w.dT_own;
-            w.dT_ld = D;
-            w.dA_own = mimic ? ar.take<float>((size_t)dA_rows * D) : nullptr;
-            w.dA = w.dA_own;
-            w.dA_ld = D;
-            w.dA_split = dA_rows;
-        }
-        plan_slabs(ar, T, R, w);
+        TowerPlan o;
+        o.backward = true;
+        o.io = ext_io ? 0 : IO_ALL;
+        o.mimic = mimic;
+        o.dA_rows = dA_rows;
+        o.w16 = o.gw16 = true;
+        plan_tower(ar, T, R, o, w);  // the claim marks are plan_scratch's
         plan_coalesce(ar, w.co, R);
         if (A.adam_history && A.history_capacity > 1) {
             const int cap = A.history_capacity;
             catchup_bind(w.cl, ar.take<int32_t>(catchup_list_ints(R, cap)), R, cap);
         }
-        if (needs_wpad(T)) w.wpad = ar.take<float>((size_t)T.linear[0].out_features * round4(T.linear[0].in_features));
-        if (uses_w16(T)) w.w16 = ar.take<uint16_t>((size_t)T.linear[0].out_features * round8(T.linear[0].in_features));
         w.piece_e = ar.take<float>((size_t)R * T.id.dim);
         if (mimic) w.piece_a = ar.take<float>((size_t)R * D);
         if (T.id.optimizer == TTAMM_OPT_DENSE) w.side_id = ar.take<float>((size_t)R * 3 * T.id.dim);
@@ -434,585 +196,6 @@ int plan(Arena& ar, const ttamm_step_args& A, StepWs& ws) {
     carve_grads(A.user, ws.user, arena);
     carve_grads(A.item, ws.item, arena);
     return TTAMM_OK;
-}
-
-GemmProblem gp_base() {
-    GemmProblem p;
-    std::memset(&p, 0, sizeof(p));
-    p.keep_prob = 1.f;
-    p.inv_keep = 1.f;
-    p.a_ones_col = -1;
-    return p;
-}
-
-struct Batcher {
-    GemmBatch b;
-    Batcher() { std::memset(&b, 0, sizeof(b)); }
-    void add(const GemmProblem& p) { b.p[b.count++] = p; }
-    int run(hipStream_t s) {
-        if (b.count == 0) return TTAMM_OK;
-        int rc = launch_gemm(b, s);
-        std::memset(&b, 0, sizeof(b));
-        return rc;
-    }
-};
-
-// Dropout RNG words: key = seed; counter words 2,3 = step counter / (domain | tower | layer)
-void set_dropout(GemmProblem& p, const ttamm_tower& T, const ttamm_batch& bt, int tower_id, int layer,
-                 const uint8_t* mask) {
-    const float pdrop = T.dropout;
-    p.keep_prob = 1.0f - pdrop;
-    // torch computes noise/(1-p) in fp32: 1.f / (1.f - p)
-    p.inv_keep = pdrop > 0.f ? 1.0f / (1.0f - pdrop) : 1.0f;
-    p.keep_mask = mask;
-    p.rng_k0 = (uint32_t)bt.seed;
-    p.rng_k1 = (uint32_t)(bt.seed >> 32);
-    p.rng_c2 = (uint32_t)bt.counter;
-    p.rng_c3 = RNG_DROPOUT | ((uint32_t)tower_id << 24) | ((uint32_t)layer << 20) |
-               ((uint32_t)(bt.counter >> 32) & 0xFFFFFu);
-}
-
-void set_keys(GemmProblem& p, const TowerWs& w) {
-    p.row_key = w.row_key;
-    p.key_base0 = w.key_base0;
-    p.key_base1 = w.key_base1;
-    p.key_split = w.key_split;
-}
-
-// ---- fused gate (gate.hip) ------------------------------------------------------------------
-// Used when every gated tower of a grouped launch has a supported D == Hg: fp32 towers gate.hip
-// (D in {32, 64, 96, 128}), bf16 towers gate16.hip (D in {128, 256}); any other configuration runs
-// the generic GEMM path.  TTAMM_GENERIC_GATE=1 forces the generic path (the tests run both).
-bool generic_gate_forced() {
-    const char* v = product_env("TTAMM_GENERIC_GATE");
-    return v && v[0] == '1';
-}
-
-// Whether the gated towers of a grouped launch all run on one fused gate kernel, and which: their
-// common hidden width and form (planes 0: gate.hip, 1 / 3: gate16.hip).  has16[k]: tower k has
-// gate16 weight images (plan() gives a gated tower some exactly when gate16_supported).
-bool gate_choice(const ttamm_tower* const* T, const bool* has16, int ntowers, int D, int& hg, int& planes) {
-    hg = planes = -1;
-    if (generic_gate_forced()) return false;
-    // TTAMM_GATE16_SPLIT=1: fp32 towers at D = 96 on gate16.hip's split-bf16 form instead of gate.hip
-    // (fp32 MFMA).  Measured slower at C2 (forward 71 vs 61 us, backward 72 vs 70, step 0.695 vs
-    // 0.655 ms, profiles/r05_s20_gate16_split.txt): the kernels are latency-bound, not MFMA-bound
-    const char* e16 = dev_env("TTAMM_GATE16_SPLIT");
-    const bool split16 = e16 && e16[0] == '1';
-    for (int k = 0; k < ntowers; ++k) {
-        const ttamm_tower& t = *T[k];
-        if (t.fusion != TTAMM_FUSION_GATED) continue;
-        const int h = t.gate[0].out_features;
-        int np;
-        if (t.matmul_bf16) {
-            if (!(gate16_supported(D, h, 1) && has16[k])) return false;
-            np = 1;
-        } else if (split16 && gate16_supported(D, h, 3) && has16[k]) {
-            np = 3;
-        } else if (gate_fused_supported(D, h)) {
-            np = 0;
-        } else {
-            return false;
-        }
-        if ((hg >= 0 && h != hg) || (planes >= 0 && np != planes)) return false;
-        hg = h;
-        planes = np;
-    }
-    return hg >= 0;
-}
-
-bool gate_group(const ttamm_tower* const* T, TowerWs* const* W, int ntowers, int D, bool mimic, GateArgs& ga) {
-    std::memset(&ga, 0, sizeof(ga));
-    bool has16[2] = {};
-    for (int k = 0; k < ntowers; ++k) has16[k] = W[k]->gw16 != nullptr;
-    int hg, planes;
-    if (!gate_choice(T, has16, ntowers, D, hg, planes)) return false;
-    ga.planes = planes;
-    ga.images_ready = 1;
-    for (int k = 0; k < ntowers; ++k) {
-        const ttamm_tower& t = *T[k];
-        const TowerWs& w = *W[k];
-        if (t.fusion != TTAMM_FUSION_GATED || w.R <= 0) continue;
-        GateTower& g = ga.tw[ga.count++];
-        g.R = w.R;
-        g.ef = w.ef;
-        g.G1 = t.gate[0].weight;
-        g.c1 = t.gate[0].bias;
-        g.G2 = t.gate[1].weight;
-        g.c2 = t.gate[1].bias;
-        g.z = w.z;
-        g.g = w.g;
-        g.t = w.t;
-        g.a = w.a;
-        g.ld_t = w.t_ld;
-        g.table = mimic ? t.mimic.weight : nullptr;
-        g.idx = w.idx;
-        g.aug = w.aug;
-        g.dT = w.dT;
-        g.ld_dT = w.dT_ld;
-        g.dq = w.dq;
-        g.dz = w.dz;
-        g.dEF = w.dEF;
-        g.xu = w.xu;
-        g.w16 = w.gw16;
-        if (!w.gw16_ready) ga.images_ready = 0;
-    }
-    ga.D = D;
-    ga.HG = hg;
-    return true;
-}
-
-// compact exchange rows (TowerWs::xu) are addressed by the fused gate kernels only
-int require_fused_for_units(const ttamm_tower* const* T, TowerWs* const* W, int ntowers, bool fused_gate) {
-    for (int k = 0; k < ntowers; ++k)
-        TTAMM_REQUIRE(!W[k]->xu || (T[k]->fusion == TTAMM_FUSION_GATED && fused_gate),
-                      "compact exchange rows (exchange_counts) need the item tower on the fused gate kernels "
-                      "(ttamm_exchange_compact_supported)");
-    return TTAMM_OK;
-}
-
-// ---- forward -------------------------------------------------------------------------------
-// part FWD_GATHER: ID-row renorm + gather; FWD_FEAT: feature encoder; FWD_FUSION: gate / combine
-// (reads the mimic rows)
-// TTAMM_GATE_OUT_EPILOGUE=1: the generic gate's sigmoid mix / mimic augment in the second gate
-// GEMM's epilogue (EPI_GATE_OUT) instead of gate_mix_kernel after an EPI_STORE launch
-bool gate_out_epilogue() {
-    static const bool on = dev_env("TTAMM_GATE_OUT_EPILOGUE") != nullptr;
-    return on;
-}
-enum { FWD_GATHER = 1, FWD_FUSION = 2, FWD_FEAT = 4, FWD_MLP = FWD_GATHER | FWD_FEAT, FWD_ALL = 7 };
-int forward_fusion(const ttamm_tower* T[2], TowerWs* W[2], int D, bool mimic, hipStream_t s, int ntowers);
-int tower_forward(const ttamm_tower* T[2], TowerWs* W[2], const ttamm_batch& bt, int D, bool mimic, hipStream_t s,
-                  int ntowers, void* const* l0_events = nullptr, int part = FWD_ALL, hipEvent_t after_l0 = nullptr) {
-    int rc;
-    if (part & FWD_GATHER) {
-        // ID rows -> e (ef[:, :D] when gated): both towers' gathers in one launch
-        GatherSegs gs;
-        gs.count = 0;
-        for (int k = 0; k < ntowers; ++k) {
-            const ttamm_tower& t = *T[k];
-            TowerWs& w = *W[k];
-            if (t.id.max_norm > 0.0 && w.R > 0 && w.row_key && w.renorm_key_split > 0) {
-                // sharded owner: every requester's positives (keys < global batch) are the reference's
-                // first item lookup (training.py:750), the negatives its second (:776)
-                for (int ph = 0; ph < 2; ++ph)
-                    if ((rc = launch_renorm_rows(t.id.weight, t.id.rows, t.id.dim, w.idx, w.R, t.id.max_norm, w.renorm_mark,
-                                                 w.renorm_tag + ph, s, w.row_key, w.renorm_key_split, ph)))
-                        return rc;
-            } else if (t.id.max_norm > 0.0 && w.R > 0) {  // nn.Embedding max_norm: renorm, then look up
-                const int64_t split = w.renorm_split > 0 && w.renorm_split < w.R ? w.renorm_split : w.R;
-                if ((rc = launch_renorm_rows(t.id.weight, t.id.rows, t.id.dim, w.idx, split, t.id.max_norm, w.renorm_mark,
-                                             w.renorm_tag, s)))
-                    return rc;
-                if (split < w.R &&
-                    (rc = launch_renorm_rows(t.id.weight, t.id.rows, t.id.dim, w.idx + split, w.R - split, t.id.max_norm,
-                                             w.renorm_mark, w.renorm_tag + 1, s)))
-                    return rc;
-            }
-            float* dst = uses_ef(t) ? w.ef : w.e;
-            const int64_t ld = uses_ef(t) ? efw(t) : t.id.dim;
-            gs.seg[gs.count++] = GatherSeg{t.id.weight, t.id.rows, t.id.dim, w.idx, w.R, dst, ld};
-        }
-        if ((rc = launch_gather_rows_segs(gs, s))) return rc;
-    }
-    if (part & FWD_FEAT) {
-        for (int k = 0; k < ntowers; ++k) {
-            const ttamm_tower& t = *T[k];
-            TowerWs& w = *W[k];
-            if (t.fusion != TTAMM_FUSION_IDENTITY && t.n_linear == 0 && w.R > 0) {
-                // identity feature encoder (encoders.py:114-119): f = the feature row
-                const int64_t ld = uses_ef(t) ? efw(t) : t.id.dim;
-                float* fdst = uses_ef(t) ? w.ef + t.id.dim : w.f;
-                if ((rc = launch_add_rows(t.features, t.feat_ld, nullptr, 0, w.R, fo_dim(t), fdst, ld, s, w.fidx)))
-                    return rc;
-            }
-        }
-        // feature encoder layers
-        int maxL = 0;
-        for (int k = 0; k < ntowers; ++k)
-            if (T[k]->fusion != TTAMM_FUSION_IDENTITY) maxL = T[k]->n_linear > maxL ? T[k]->n_linear : maxL;
-        for (int l = 0; l < maxL; ++l) {
-            Batcher bb;
-            PadSegs pads;  // first-layer weights padded to 16-B rows, both towers in one launch
-            pads.count = 0;
-            for (int k = 0; k < ntowers; ++k) {
-                const ttamm_tower& t = *T[k];
-                TowerWs& w = *W[k];
-                if (t.fusion == TTAMM_FUSION_IDENTITY || l >= t.n_linear) continue;
-                const ttamm_linear& L = t.linear[l];
-                GemmProblem p = gp_base();
-                p.bf16 = t.matmul_bf16;
-                if (l == 0) {
-                    p.A = t.features;
-                    p.a_idx = w.fidx;
-                    p.lda = t.feat_ld;
-                } else {
-                    p.A = w.hid[l - 1];
-                    p.lda = t.linear[l - 1].out_features;
-                }
-                p.B = L.weight;
-                p.ldb = L.in_features;
-                if (l == 0 && w.w16) {  // bf16 operands in memory (C5 layer 1)
-                    const int kp = round8(L.in_features);
-                    if ((rc = launch_to_bf16(L.weight, L.out_features, L.in_features, L.in_features, w.w16, kp, s)))
-                        return rc;
-                    p.A16 = t.features_bf16;
-                    p.lda = t.feat_bf16_ld;
-                    p.B16 = w.w16;
-                    p.ldb = kp;
-                } else if (l == 0 && w.wpad) {
-                    pads.seg[pads.count++] = PadSeg{L.weight, L.out_features, L.in_features, L.in_features, w.wpad,
-                                                    round4(L.in_features)};
-                    p.B = w.wpad;
-                    p.ldb = round4(L.in_features);
-                }
-                p.b_kn = 0;
-                p.M = (int)w.R;
-                p.N = L.out_features;
-                p.K = L.in_features;
-                // the feature rows and the padded weight are zero beyond F: run K to the padded
-                // width so every k-tile is whole (fast GEMM path)
-                if (l == 0 && w.wpad && t.feat_ld >= round4(L.in_features)) p.K = round4(L.in_features);
-                if (l == 0 && w.w16) p.K = round8(L.in_features);  // both operands zero beyond F
-                // pre-split feature rows (ttamm_tower.features_planes): zero beyond F up to whole
-                // 16-k chunks, so K may run to the padded width
-                if (l == 0 && t.features_planes && !t.matmul_bf16 && p.K <= 16 * (t.feat_planes_ld / 48)) {
-                    p.A3p = t.features_planes;
-                    p.lda3 = t.feat_planes_ld;
-                }
-                p.bias = L.bias;
-                if (l + 1 < t.n_linear) {
-                    p.epi = EPI_HIDDEN;
-                    p.C = w.hid[l];
-                    p.ldc = L.out_features;
-                    const uint8_t* injected = w.role == ROLE_USER ? bt.user_keep_mask[l] : bt.item_keep_mask[l];
-                    set_dropout(p, t, bt, w.role, l, injected);
-                    set_keys(p, w);
-                    p.act = t.activation;
-                    if (t.activation != TTAMM_ACT_RELU) {  // the backward's inputs
-                        p.pre = w.pre[l];
-                        if (t.dropout > 0.f && injected == nullptr) p.mask_out = w.mask[l];
-                        w.keep[l] = injected ? injected : w.mask[l];
-                    }
-                } else {
-                    p.epi = EPI_STORE;
-                    if (uses_ef(t)) {
-                        p.C = w.ef + t.id.dim;
-                        p.ldc = efw(t);
-                    } else {
-                        p.C = w.f;
-                        p.ldc = D;
-                    }
-                }
-                bb.add(p);
-            }
-            if ((rc = launch_pad_rows_segs(pads, s))) return rc;
-            const bool timed = l == 0 && l0_events && l0_events[0] && l0_events[1];
-            if (timed) TTAMM_HIP(hipEventRecord((hipEvent_t)l0_events[0], s));
-            if ((rc = bb.run(s))) return rc;
-            if (timed) TTAMM_HIP(hipEventRecord((hipEvent_t)l0_events[1], s));
-            if (l == 0 && after_l0) TTAMM_HIP(hipEventRecord(after_l0, s));
-        }
-    }
-    return part & FWD_FUSION ? forward_fusion(T, W, D, mimic, s, ntowers) : TTAMM_OK;
-}
-
-// part FWD_FUSION: the gate (fused kernel or two GEMMs + mix), the concat projection, or the combine
-int forward_fusion(const ttamm_tower* T[2], TowerWs* W[2], int D, bool mimic, hipStream_t s, int ntowers) {
-    int rc;
-    GateArgs ga;
-    const bool fused_gate = gate_group(T, W, ntowers, D, mimic, ga);
-    if ((rc = require_fused_for_units(T, W, ntowers, fused_gate))) return rc;
-    if (fused_gate && ga.count > 0) {
-        if ((rc = launch_gate(ga, false, s))) return rc;
-        for (int k = 0; k < ntowers; ++k) W[k]->gw16_ready = W[k]->gw16 != nullptr;
-    }
-    Batcher g1, g2, gc;
-    for (int k = 0; k < ntowers; ++k) {
-        const ttamm_tower& t = *T[k];
-        TowerWs& w = *W[k];
-        const float* table = mimic ? t.mimic.weight : nullptr;
-        if (t.fusion == TTAMM_FUSION_CONCAT) {  // t = [e | f] P^T + b (encoders.py:242-244)
-            GemmProblem p = gp_base();
-            p.bf16 = t.matmul_bf16;
-            p.A = w.ef;
-            p.lda = efw(t);
-            p.B = t.gate[0].weight;
-            p.ldb = efw(t);
-            p.M = (int)w.R;
-            p.N = D;
-            p.K = efw(t);
-            p.bias = t.gate[0].bias;
-            p.epi = EPI_STORE;
-            p.C = w.t;
-            p.ldc = w.t_ld;
-            gc.add(p);
-            continue;
-        }
-        if (t.fusion == TTAMM_FUSION_GATED) {
-            if (fused_gate) continue;
-            const int Hg = t.gate[0].out_features;
-            GemmProblem p = gp_base();
-            p.bf16 = t.matmul_bf16;
-            p.A = w.ef;
-            p.lda = 2 * D;
-            p.B = t.gate[0].weight;
-            p.ldb = 2 * D;
-            p.M = (int)w.R;
-            p.N = Hg;
-            p.K = 2 * D;
-            p.bias = t.gate[0].bias;
-            p.epi = EPI_GATE_HIDDEN;
-            p.C = w.z;
-            p.ldc = Hg;
-            g1.add(p);
-            GemmProblem q = gp_base();
-            q.bf16 = t.matmul_bf16;
-            q.A = w.z;
-            q.lda = Hg;
-            q.B = t.gate[1].weight;
-            q.ldb = Hg;
-            q.M = (int)w.R;
-            q.N = D;
-            q.K = Hg;
-            q.bias = t.gate[1].bias;
-            if (gate_out_epilogue()) {  // TTAMM_GATE_OUT_EPILOGUE=1: the mix in the GEMM's epilogue
-                q.epi = EPI_GATE_OUT;
-                q.C = w.aug;
-                q.ldc = D;
-                q.aux0 = w.ef;
-                q.ld_aux0 = 2 * D;
-                q.out1 = w.g;
-                q.out2 = w.t;
-                q.out3 = w.a;
-                q.table = table;
-                q.idx = w.idx;
-                q.ld_out = D;
-                q.ld_out2 = w.t_ld;
-            } else {  // the pre-activation into g; gate_mix_kernel below (rows.hip)
-                q.epi = EPI_STORE;
-                q.C = w.g;
-                q.ldc = D;
-            }
-            g2.add(q);
-        } else {
-            if ((rc = launch_combine(w.e, D, t.fusion == TTAMM_FUSION_SUM ? w.f : nullptr, D, table, t.mimic.rows, w.idx,
-                                     w.R, D, w.t, w.a, w.t_ld, w.aug, s)))
-                return rc;
-        }
-    }
-    if ((rc = g1.run(s))) return rc;
-    if ((rc = g2.run(s))) return rc;
-    if (!gate_out_epilogue() && !fused_gate) {
-        for (int k = 0; k < ntowers; ++k) {
-            const ttamm_tower& t = *T[k];
-            TowerWs& w = *W[k];
-            if (t.fusion != TTAMM_FUSION_GATED) continue;
-            if ((rc = launch_gate_mix(w.g, w.ef, mimic ? t.mimic.weight : nullptr, w.idx, w.R, D, w.t, w.a, w.t_ld, w.aug, s)))
-                return rc;
-        }
-    }
-    if ((rc = gc.run(s))) return rc;
-    for (int k = 0; k < ntowers; ++k) {  // concat: a = A[idx], aug = t + a (in place on t)
-        const ttamm_tower& t = *T[k];
-        TowerWs& w = *W[k];
-        if (t.fusion != TTAMM_FUSION_CONCAT) continue;
-        if ((rc = launch_combine(w.t, w.t_ld, nullptr, D, mimic ? t.mimic.weight : nullptr, t.mimic.rows, w.idx, w.R,
-                                 D, w.t, w.a, w.t_ld, w.aug, s)))
-            return rc;
-    }
-    return TTAMM_OK;
-}
-
-// TTAMM_WGRAD_X16=1: the bf16 towers' first-layer weight gradient reads X from the bf16 feature copy
-bool wgrad_x16() {
-    const char* e = dev_env("TTAMM_WGRAD_X16");
-    return e && e[0] == '1';
-}
-
-// ---- backward ------------------------------------------------------------------------------
-// wg_events (optional, 2 events): around the wide weight-gradient GEMM launch (bench)
-// part BWD_GATE: the fusion's backward (dEF, the ID rows' gradient with it); BWD_MLP: the feature
-// MLP's dgrad chain and every weight gradient
-enum { BWD_GATE = 1, BWD_MLP = 2, BWD_ALL = 3 };
-int tower_wgrads(const ttamm_tower* T[2], TowerWs* W[2], int D, hipStream_t s, int ntowers, void* const* wg_events);
-int tower_backward(const ttamm_tower* T[2], TowerWs* W[2], int D, hipStream_t s, int ntowers,
-                   void* const* wg_events = nullptr, int part = BWD_ALL) {
-    int rc;
-    if (part & BWD_GATE) {
-    // gate: dq, dz, dEF
-    GateArgs ga;
-    const bool fused_gate = gate_group(T, W, ntowers, D, false, ga);
-    if ((rc = require_fused_for_units(T, W, ntowers, fused_gate))) return rc;
-    if (fused_gate && ga.count > 0)
-        if ((rc = launch_gate(ga, true, s))) return rc;
-    Batcher b1, b2;
-    for (int k = 0; k < ntowers; ++k) {
-        const ttamm_tower& t = *T[k];
-        TowerWs& w = *W[k];
-        if (t.fusion != TTAMM_FUSION_GATED || fused_gate) continue;
-        const int Hg = t.gate[0].out_features;
-        if ((rc = launch_gate_dq(w.dT, w.dT_ld, w.ef, w.g, w.R, D, w.dq, s))) return rc;
-        GemmProblem p = gp_base();  // dz = (dq . G2) * (z > 0)
-        p.bf16 = t.matmul_bf16;
-        p.A = w.dq;
-        p.lda = D;
-        p.B = t.gate[1].weight;  // [D, Hg] = [K, N]
-        p.ldb = Hg;
-        p.b_kn = 1;
-        p.M = (int)w.R;
-        p.N = Hg;
-        p.K = D;
-        p.epi = EPI_DGRAD_RELU;
-        p.C = w.dz;
-        p.ldc = Hg;
-        p.aux0 = w.z;
-        p.ld_aux0 = Hg;
-        b1.add(p);
-        GemmProblem q = gp_base();  // [de | df] = dz . G1 + gate-mix terms
-        q.bf16 = t.matmul_bf16;
-        q.A = w.dz;
-        q.lda = Hg;
-        q.B = t.gate[0].weight;  // [Hg, 2D] = [K, N]
-        q.ldb = 2 * D;
-        q.b_kn = 1;
-        q.M = (int)w.R;
-        q.N = 2 * D;
-        q.K = Hg;
-        q.epi = EPI_DGRAD_GATE_EF;
-        q.C = w.dEF;
-        q.ldc = 2 * D;
-        q.aux1 = w.dT;
-        q.ld_aux1 = w.dT_ld;
-        q.aux2 = w.g;
-        q.ld_aux2 = D;
-        b2.add(q);
-    }
-    for (int k = 0; k < ntowers; ++k) {  // concat: d[e | f] = dT P
-        const ttamm_tower& t = *T[k];
-        TowerWs& w = *W[k];
-        if (t.fusion != TTAMM_FUSION_CONCAT) continue;
-        GemmProblem q = gp_base();
-        q.bf16 = t.matmul_bf16;
-        q.A = w.dT;
-        q.lda = w.dT_ld;
-        q.B = t.gate[0].weight;  // [D, Did + Fo] = [K, N]
-        q.ldb = efw(t);
-        q.b_kn = 1;
-        q.M = (int)w.R;
-        q.N = efw(t);
-        q.K = D;
-        q.epi = EPI_STORE;
-        q.C = w.dEF;
-        q.ldc = efw(t);
-        b2.add(q);
-    }
-    if ((rc = b1.run(s))) return rc;
-    if ((rc = b2.run(s))) return rc;
-    }
-    if (!(part & BWD_MLP)) return TTAMM_OK;
-    // MLP dgrad chain (layers L-1 .. 1)
-    int maxL = 0;
-    for (int k = 0; k < ntowers; ++k)
-        if (T[k]->fusion != TTAMM_FUSION_IDENTITY) maxL = T[k]->n_linear > maxL ? T[k]->n_linear : maxL;
-    for (int step = 0; step + 1 < maxL; ++step) {
-        Batcher bb;
-        for (int k = 0; k < ntowers; ++k) {
-            const ttamm_tower& t = *T[k];
-            TowerWs& w = *W[k];
-            if (t.fusion == TTAMM_FUSION_IDENTITY) continue;
-            const int l = t.n_linear - 1 - step;  // layer whose input grad we compute
-            if (l < 1) continue;
-            const ttamm_linear& L = t.linear[l];
-            GemmProblem p = gp_base();
-            p.bf16 = t.matmul_bf16;
-            if (l == t.n_linear - 1) {
-                p.A = uses_ef(t) ? w.dEF + t.id.dim : w.dT;
-                p.lda = uses_ef(t) ? efw(t) : w.dT_ld;
-            } else {
-                p.A = w.dhid[l];
-                p.lda = L.out_features;
-            }
-            p.B = L.weight;  // [out, in] = [K, N]
-            p.ldb = L.in_features;
-            p.b_kn = 1;
-            p.M = (int)w.R;
-            p.N = L.in_features;
-            p.K = L.out_features;
-            p.epi = EPI_DGRAD_HIDDEN;
-            p.C = w.dhid[l - 1];
-            p.ldc = L.in_features;
-            p.aux0 = w.hid[l - 1];
-            p.ld_aux0 = L.in_features;
-            const float pdrop = t.dropout;
-            p.inv_keep = pdrop > 0.f ? 1.0f / (1.0f - pdrop) : 1.0f;
-            p.act = t.activation;
-            if (t.activation != TTAMM_ACT_RELU) {  // act'(pre-activation), the forward's keep bytes
-                p.aux0 = w.pre[l - 1];
-                p.keep_prob = 1.0f - pdrop;
-                p.keep_mask = pdrop > 0.f ? w.keep[l - 1] : nullptr;
-            }
-            bb.add(p);
-        }
-        if ((rc = bb.run(s))) return rc;
-    }
-    return tower_wgrads(T, W, D, s, ntowers, wg_events);
-}
-
-// dW = dY^T X ([M, N]) and db = sum dY over the tower's rows, into the gradient arena through `slab`
-WgradProblem wgrad_problem(const ttamm_tower& t, const TowerWs& w, const float* dY, int64_t ld_dy, const float* X,
-                           int64_t ld_x, int M, int N, float* grad_w, float* grad_b, float* slab) {
-    WgradProblem p{};
-    p.bf16 = t.matmul_bf16;
-    p.dY = dY, p.ld_dy = ld_dy;
-    p.X = X, p.ld_x = ld_x;
-    p.R = (int)w.R, p.M = M, p.N = N;
-    p.grad_w = grad_w, p.grad_b = grad_b, p.slab = slab;
-    p.rows_per_split = w.wgrad_rps[wgrad_class(M)];
-    return p;
-}
-
-// all weight gradients in one grouped launch
-int tower_wgrads(const ttamm_tower* T[2], TowerWs* W[2], int D, hipStream_t s, int ntowers, void* const* wg_events) {
-    WgradBatch wb;
-    std::memset(&wb, 0, sizeof(wb));
-    for (int k = 0; k < ntowers; ++k) {
-        const ttamm_tower& t = *T[k];
-        TowerWs& w = *W[k];
-        if (t.fusion == TTAMM_FUSION_IDENTITY) continue;
-        float* const* gslab = w.slab + TTAMM_MAX_LINEAR;
-        if (t.fusion == TTAMM_FUSION_GATED) {
-            const int Hg = t.gate[0].out_features;
-            wb.p[wb.count++] = wgrad_problem(t, w, w.dq, D, w.z, Hg, D, Hg, w.ggw[1], w.ggb[1], gslab[1]);
-            wb.p[wb.count++] = wgrad_problem(t, w, w.dz, Hg, w.ef, 2 * D, Hg, 2 * D, w.ggw[0], w.ggb[0], gslab[0]);
-        }
-        if (t.fusion == TTAMM_FUSION_CONCAT)  // dP = dT^T [e | f], db = sum dT
-            wb.p[wb.count++] =
-                wgrad_problem(t, w, w.dT, w.dT_ld, w.ef, efw(t), D, efw(t), w.ggw[0], w.ggb[0], gslab[0]);
-        for (int l = t.n_linear - 1; l >= 0; --l) {
-            const ttamm_linear& L = t.linear[l];
-            const bool last = l == t.n_linear - 1;
-            const float* dY = !last ? w.dhid[l] : uses_ef(t) ? w.dEF + t.id.dim : w.dT;
-            const int64_t ld_dy = !last ? L.out_features : uses_ef(t) ? efw(t) : w.dT_ld;
-            WgradProblem p = l == 0 ? wgrad_problem(t, w, dY, ld_dy, t.features, t.feat_ld, L.out_features,
-                                                    L.in_features, w.gw[l], w.gb[l], w.slab[l])
-                                    : wgrad_problem(t, w, dY, ld_dy, w.hid[l - 1], t.linear[l - 1].out_features,
-                                                    L.out_features, L.in_features, w.gw[l], w.gb[l], w.slab[l]);
-            if (l == 0) {
-                p.x_idx = w.fidx;
-                if (uses_w16(t) && wgrad_x16()) {  // the same bf16 values, from the tower's bf16 copy
-                    p.X16 = t.features_bf16;
-                    p.ld_x16 = t.feat_bf16_ld;
-                }
-                if (t.features_planes && !t.matmul_bf16) {
-                    p.X3p = t.features_planes;
-                    p.ld_x3 = t.feat_planes_ld;
-                }
-            }
-            wb.p[wb.count++] = p;
-        }
-    }
-    return launch_wgrad(wb, s, wg_events);
 }
 
 // Deferred exact AdamW(g = 0) (ttamm.h ttamm_table.last_step).
@@ -1743,10 +926,7 @@ int validate_step(const ttamm_step_args& A) {
     int rc;
     TTAMM_REQUIRE(A.table_g0_math == TTAMM_G0_EXACT || A.table_g0_math == TTAMM_G0_FAST,
                   "table_g0_math must be TTAMM_G0_EXACT or TTAMM_G0_FAST");
-    if ((rc = validate_tower(A.user, "user_encoder", D, true))) return rc;
-    if ((rc = validate_tower(A.item, "item_encoder", D, true))) return rc;
-    TTAMM_REQUIRE(out_dim(A.item) == D, "User and item encoders must produce embeddings with the same dimension.");
-    TTAMM_REQUIRE(A.user.matmul_bf16 == A.item.matmul_bf16, "user and item towers must share one matmul precision");
+    if ((rc = validate_pair(A, true))) return rc;
     if (A.hp.grad_clip_norm > 0.0 && A.mimic_enabled)
         TTAMM_REQUIRE(A.user.id.dim == D && A.item.id.dim == D,
                       "gradient clipping with a concat output_dim other than the embedding dim is not supported");
@@ -1772,12 +952,7 @@ int validate_step(const ttamm_step_args& A) {
     }
     const int64_t num_items = A.num_items_global > 0 ? A.num_items_global : A.item.id.rows;
     TTAMM_REQUIRE(num_items > 1, "num_items must be greater than one.");
-    if (A.mimic_enabled) {
-        TTAMM_REQUIRE(A.user.mimic.weight && A.item.mimic.weight, "mimic tables missing");
-        TTAMM_REQUIRE(A.user.mimic.dim == D && A.item.mimic.dim == D &&
-                          A.user.mimic.rows == A.user.id.rows && A.item.mimic.rows == A.item.id.rows,
-                      "Adaptive mimic requires user and item embedding dimensions to match.");
-    }
+    if ((rc = validate_mimic_pair(A))) return rc;
     TTAMM_REQUIRE(A.hp.dense_step >= 1 && A.hp.sparse_step >= 1, "optimizer step counts must be >= 1");
     TTAMM_REQUIRE(A.hp.dense_optimizer == TTAMM_DENSE_ADAM || A.hp.dense_optimizer == TTAMM_DENSE_SGD,
                   "hp.dense_optimizer must be TTAMM_DENSE_ADAM or TTAMM_DENSE_SGD");
@@ -2191,415 +1366,6 @@ int flush_tables(const ttamm_step_args& A, hipStream_t s) {
     if ((rc = launch_replay(ra, pl.aux))) return rc;
     TTAMM_HIP(hipEventRecord(pl.ev[EV_FROM_AUX], pl.aux));
     TTAMM_HIP(hipStreamWaitEvent(s, pl.ev[EV_FROM_AUX], 0));
-    return TTAMM_OK;
-}
-
-// ---- eval-mode tower forward (TowerEncoder.forward + augment) -----------------------------
-size_t tower_forward_workspace_size(const ttamm_tower& T, int64_t n) {
-    Arena ar{nullptr, 0, 0, true};
-    const int D = out_dim(T);
-    for (int l = 0; l + 1 < T.n_linear; ++l) ar.take<float>((size_t)n * T.linear[l].out_features);
-    ar.take<float>((size_t)n * efw(T));  // ef / e
-    ar.take<float>((size_t)n * D);       // f
-    if (T.fusion == TTAMM_FUSION_GATED) ar.take<float>((size_t)n * T.gate[0].out_features);
-    for (int q = 0; q < 3; ++q) ar.take<float>((size_t)n * D);  // g, t, a
-    ar.take<int64_t>(n);                                         // range-checked ids
-    if (needs_wpad(T)) ar.take<float>((size_t)T.linear[0].out_features * round4(T.linear[0].in_features));
-    if (T.id.max_norm > 0.0) ar.take<int32_t>(T.id.rows);  // renorm claim marks
-    return ar.off + 256;
-}
-
-int tower_forward_eval(const ttamm_tower& T, const int64_t* idx, const int64_t* fidx, int64_t n, int augment,
-                       float* out, void* wsp, size_t ws_bytes, hipStream_t s) {
-    const int D = out_dim(T);
-    int rc;
-    if ((rc = validate_tower(T, "tower", D, false))) return rc;
-    if (augment && T.mimic.weight)
-        TTAMM_REQUIRE(T.mimic.rows == T.id.rows && T.mimic.dim == D, "tower: mimic table shape does not match the tower");
-    if (n <= 0) return TTAMM_OK;
-    Arena ar{static_cast<char*>(wsp), ws_bytes, 0, false};
-    TowerWs w;
-    w.R = n;
-    w.idx = idx;
-    w.fidx = fidx;
-    for (int l = 0; l + 1 < T.n_linear; ++l) w.hid[l] = ar.take<float>((size_t)n * T.linear[l].out_features);
-    float* efbuf = ar.take<float>((size_t)n * efw(T));
-    float* fbuf = ar.take<float>((size_t)n * D);
-    float* zbuf = T.fusion == TTAMM_FUSION_GATED ? ar.take<float>((size_t)n * T.gate[0].out_features) : nullptr;
-    float* gbuf = ar.take<float>((size_t)n * D);
-    float* tbuf = ar.take<float>((size_t)n * D);
-    float* abuf = ar.take<float>((size_t)n * D);
-    int64_t* idxc = ar.take<int64_t>(n);
-    if (needs_wpad(T)) w.wpad = ar.take<float>((size_t)T.linear[0].out_features * round4(T.linear[0].in_features));
-    if (T.id.max_norm > 0.0) {  // nn.Embedding max_norm renorms in eval mode too (one lookup)
-        w.renorm_mark = ar.take<int32_t>(T.id.rows);
-        w.renorm_tag = 1;
-    }
-    TTAMM_REQUIRE(ar.ok(), "workspace too small for tower forward");
-    if (w.renorm_mark) TTAMM_HIP(hipMemsetAsync(w.renorm_mark, 0, (size_t)T.id.rows * sizeof(int32_t), s));
-    {  // ids outside the tables read row 0 (the Python mirror raises IndexError before calling)
-        StageArgs st;
-        std::memset(&st, 0, sizeof(st));
-        st.seg[st.count++] = StageSeg{idx, idxc, n, T.id.rows};
-        if ((rc = launch_stage_rows(st, s))) return rc;
-        if (fidx == idx) fidx = idxc;
-        idx = idxc;
-        w.idx = idx;
-        w.fidx = fidx;
-    }
-    if (uses_ef(T)) {
-        w.ef = efbuf;
-        w.z = zbuf;
-        w.g = gbuf;
-    } else {
-        w.e = efbuf;
-        w.f = fbuf;
-    }
-    w.t = tbuf;
-    w.t_ld = D;
-    w.a = abuf;
-    w.aug = out;
-    // eval mode: no dropout
-    ttamm_tower te = T;
-    te.dropout = 0.f;
-    ttamm_batch bt;
-    std::memset(&bt, 0, sizeof(bt));
-    const ttamm_tower* TT[2] = {&te, nullptr};
-    TowerWs* WW[2] = {&w, nullptr};
-    const bool mimic = augment && T.mimic.weight;
-    if ((rc = tower_forward(TT, WW, bt, D, mimic, s, 1))) return rc;
-    return TTAMM_OK;
-}
-
-// ---- validation loss: one forward-only batch of `_compute_loss` (training.py:854-910) --------
-//   sample negatives (b.sample_negatives)          samplers.py:11-85, the step's Philox keying
-//   stage + range-check users, [pos; neg]          bad ids set the status bit and read row 0
-//   both towers, grouped, eval mode                dropout off, max_norm renorm kept
-//                                                  (positives and negatives as two lookups)
-//   scores + BCE terms, fixed-order mean           training.py:881-907
-// Everything runs on the caller's stream.  The tables are read as they are: deferred AdamW
-// tables (ttamm_table.last_step) must have been flushed (ttamm_flush_tables;
-// FusedTrainStep.finish() does it).  No parameter or optimizer state is written, apart from the
-// max_norm renorm of the looked-up ID rows.
-namespace {
-struct EvalWs {
-    TowerWs user, item;
-    float* partials = nullptr;
-    int blocks = 0;
-    float* ib_partials = nullptr;  // in-batch pass: inbatch_loss_kernel's block sums
-    int ib_blocks = 0;
-};
-
-// Forward buffers for B and B(1+N) rows, the staged ids, the weight pads / images the forward
-// forms and the score partials: no backward buffer, gradient slab or coalesce scratch.  The
-// in-batch pass adds its kernel's block partials (nothing B x B, no slab).
-void plan_eval(Arena& ar, const ttamm_step_args& A, EvalWs& ws, bool in_batch = false) {
-    const int64_t B = A.b.batch;
-    const int N = A.b.num_neg;
-    const int D = out_dim(A.user);
-    const bool mimic = A.mimic_enabled != 0;
-    auto tower = [&](const ttamm_tower& T, TowerWs& w, int64_t R) {
-        w.R = R;
-        w.idx_own = ar.take<int64_t>(R);
-        for (int l = 0; l + 1 < T.n_linear; ++l) w.hid[l] = ar.take<float>((size_t)R * T.linear[l].out_features);
-        if (uses_ef(T)) {
-            w.ef = ar.take<float>((size_t)R * efw(T));
-        } else {
-            w.e = ar.take<float>((size_t)R * D);
-            if (T.fusion == TTAMM_FUSION_SUM) w.f = ar.take<float>((size_t)R * D);
-        }
-        if (T.fusion == TTAMM_FUSION_GATED) {
-            const int Hg = T.gate[0].out_features;
-            w.z = ar.take<float>((size_t)R * Hg);
-            w.g = ar.take<float>((size_t)R * D);
-            const int np = T.matmul_bf16 ? 1 : 3;
-            if (gate16_supported(D, Hg, np)) w.gw16 = ar.take<uint16_t>((size_t)gate16_image_elems(D, Hg, np));
-        }
-        w.t = ar.take<float>((size_t)R * D);
-        w.a = mimic ? ar.take<float>((size_t)R * D) : nullptr;
-        w.t_ld = D;
-        w.aug = ar.take<float>((size_t)R * D);
-        if (needs_wpad(T)) w.wpad = ar.take<float>((size_t)T.linear[0].out_features * round4(T.linear[0].in_features));
-        if (uses_w16(T)) w.w16 = ar.take<uint16_t>((size_t)T.linear[0].out_features * round8(T.linear[0].in_features));
-        if (T.id.max_norm > 0.0) w.renorm_mark = ar.take<int32_t>(T.id.rows);
-    };
-    ws.user.role = ROLE_USER;
-    ws.item.role = ROLE_ITEM;
-    tower(A.user, ws.user, B);
-    tower(A.item, ws.item, B * (1 + (int64_t)N));
-    ws.blocks = score_blocks(B, D);
-    ws.partials = ar.take<float>((size_t)ws.blocks);
-    if (in_batch) {
-        ws.ib_blocks = inbatch_loss_blocks(B, B);
-        ws.ib_partials = ar.take<float>((size_t)ws.ib_blocks);
-    }
-}
-
-int validate_eval(const ttamm_step_args& A, bool in_batch = false) {
-    const int D = out_dim(A.user);
-    int rc;
-    if ((rc = validate_tower(A.user, "user_encoder", D, false))) return rc;
-    if ((rc = validate_tower(A.item, "item_encoder", D, false))) return rc;
-    TTAMM_REQUIRE(out_dim(A.item) == D, "User and item encoders must produce embeddings with the same dimension.");
-    TTAMM_REQUIRE(A.user.matmul_bf16 == A.item.matmul_bf16, "user and item towers must share one matmul precision");
-    TTAMM_REQUIRE(A.phase == TTAMM_PHASE_ALL, "eval loss: phase must be 0, the whole batch in one call (no sharded validation pass)");
-    if (in_batch) {  // ttamm_eval_loss_inbatch: the in_batch field is not consulted, N = 0 is legal
-        TTAMM_REQUIRE(A.b.num_neg >= 0 && A.b.num_neg <= 64,
-                      "eval loss (in-batch): b.num_neg (negatives_per_positive) must be in [0, 64]");
-        if ((rc = inbatch_loss_check(D))) return rc;
-    } else {
-        TTAMM_REQUIRE(A.in_batch == 0, "eval loss: in_batch must be 0 (_compute_loss scores sampled negatives only)");
-        if ((rc = score_eval_check(A.b.num_neg, D))) return rc;
-    }
-    TTAMM_REQUIRE(A.b.batch > 0, "empty batch");
-    if (A.mimic_enabled) {
-        TTAMM_REQUIRE(A.user.mimic.weight && A.item.mimic.weight, "mimic tables missing");
-        TTAMM_REQUIRE(A.user.mimic.dim == D && A.item.mimic.dim == D &&
-                          A.user.mimic.rows == A.user.id.rows && A.item.mimic.rows == A.item.id.rows,
-                      "Adaptive mimic requires user and item embedding dimensions to match.");
-    }
-    return TTAMM_OK;
-}
-}  // namespace
-
-size_t eval_loss_workspace_size(const ttamm_step_args& A) {
-    Arena ar{nullptr, 0, 0, true};
-    EvalWs ws;
-    plan_eval(ar, A, ws);
-    return ar.off + 256;
-}
-
-size_t eval_loss_inbatch_workspace_size(const ttamm_step_args& A) {
-    if (A.b.batch <= 0 || A.b.num_neg < 0) return 0;
-    Arena ar{nullptr, 0, 0, true};
-    EvalWs ws;
-    plan_eval(ar, A, ws, true);
-    return ar.off + 256;
-}
-
-// in_batch: ttamm_eval_loss_inbatch — the positives' logits come from S = U P^T
-// (inbatch_loss_kernel on U.aug and I.aug rows [0, B)), the scorer adds the sampled negatives'
-// terms only (none with N == 0) and one finalize divides by B (B + N).
-static int eval_loss_run(const ttamm_step_args& A, float* logits_out, bool in_batch, hipStream_t s) {
-    int rc;
-    if ((rc = validate_eval(A, in_batch))) return rc;
-    TTAMM_REQUIRE(A.loss_out && A.status && A.workspace, "eval loss: loss_out, status and workspace are required");
-    TTAMM_REQUIRE(A.b.users && A.b.pos_items, "eval loss: b.users / b.pos_items missing");
-    const int D = out_dim(A.user);
-    const bool mimic = A.mimic_enabled != 0;
-    const int64_t B = A.b.batch;
-    const int N = A.b.num_neg;
-    EvalWs ws;
-    Arena ar{static_cast<char*>(A.workspace), A.workspace_bytes, 0, false};
-    plan_eval(ar, A, ws, in_batch);
-    TTAMM_REQUIRE(ar.ok(), "workspace too small for this eval loss batch");
-    TowerWs &U = ws.user, &I = ws.item;
-    int64_t* neg_rows = I.idx_own + B;
-    const int64_t* neg_src = A.b.neg_items;
-    if (A.b.sample_negatives && N > 0) {  // the training step's draws for (seed, counter, row_base)
-        const int64_t num_items = A.num_items_global > 0 ? A.num_items_global : A.item.id.rows;
-        int64_t* dst = A.b.neg_items ? A.b.neg_items : neg_rows;
-        if ((rc = launch_sample_negatives(A.b.users, B, N, num_items, A.b.pos_offsets, A.b.pos_values, A.user.id.rows,
-                                          A.b.seed, A.b.counter, A.row_base * N, dst, nullptr, A.status, s)))
-            return rc;
-        neg_src = dst;
-    }
-    TTAMM_REQUIRE(N == 0 || neg_src != nullptr, "negatives must be given when sample_negatives == 0");
-    {
-        StageArgs st;
-        std::memset(&st, 0, sizeof(st));
-        st.status = A.status;
-        st.seg[st.count++] = StageSeg{A.b.users, U.idx_own, B, A.user.id.rows};
-        st.seg[st.count++] = StageSeg{A.b.pos_items, I.idx_own, B, A.item.id.rows};
-        if (N > 0) st.seg[st.count++] = StageSeg{neg_src, neg_rows, B * N, A.item.id.rows};
-        if ((rc = launch_stage_rows(st, s))) return rc;
-    }
-    U.idx = U.fidx = U.idx_own;
-    I.idx = I.fidx = I.idx_own;
-    // nn.Embedding(max_norm) renorms in eval mode too: the claim marks are cleared per call, the
-    // users are one lookup, the positives and the negatives the item table's two (training.py:875,887)
-    for (TowerWs* w : {&U, &I})
-        if (w->renorm_mark) {
-            const ttamm_tower& T = w == &U ? A.user : A.item;
-            TTAMM_HIP(hipMemsetAsync(w->renorm_mark, 0, (size_t)T.id.rows * sizeof(int32_t), s));
-            w->renorm_tag = 1;
-        }
-    I.renorm_split = B;
-    // eval mode: dropout off (a copy of each tower; the caller's descriptors are not changed)
-    ttamm_tower tu = A.user, ti = A.item;
-    tu.dropout = ti.dropout = 0.f;
-    ttamm_batch bt;
-    std::memset(&bt, 0, sizeof(bt));
-    const ttamm_tower* TT[2] = {&tu, &ti};
-    TowerWs* WW[2] = {&U, &I};
-    if ((rc = tower_forward(TT, WW, bt, D, mimic, s, 2))) return rc;
-    EvalScoreArgs sa;
-    std::memset(&sa, 0, sizeof(sa));
-    sa.B = B;
-    sa.N = N;
-    sa.D = D;
-    sa.user_aug = U.aug;
-    sa.item_aug = I.aug;
-    sa.ld_item = D;
-    sa.partials = ws.partials;
-    sa.blocks = ws.blocks;
-    sa.logits = logits_out;
-    if (in_batch) {
-        InBatchLossArgs ib{};
-        ib.U = U.aug, ib.ldu = D, ib.B = B, ib.P = I.aug, ib.ldp = D, ib.Bc = B, ib.D = D;
-        ib.row_base = 0;
-        ib.loss_part = ws.ib_partials;
-        if ((rc = launch_inbatch_loss(ib, s))) return rc;
-        sa.skip_pos = 1;
-        sa.logits = nullptr;  // S is never stored
-        if (N > 0 && (rc = launch_score_eval(sa, s))) return rc;
-        return launch_eval_loss_inbatch_finalize(ws.partials, N > 0 ? ws.blocks : 0, ws.ib_partials, ws.ib_blocks,
-                                                 B * (B + (int64_t)N), B, A.loss_out, A.loss_accum, A.status, s);
-    }
-    if ((rc = launch_score_eval(sa, s))) return rc;
-    return launch_eval_loss_finalize(ws.partials, ws.blocks, B * (1 + (int64_t)N), B, A.loss_out, A.loss_accum, A.status, s);
-}
-
-int eval_loss(const ttamm_step_args& A, float* logits_out, hipStream_t s) { return eval_loss_run(A, logits_out, false, s); }
-
-int eval_loss_inbatch(const ttamm_step_args& A, hipStream_t s) { return eval_loss_run(A, nullptr, true, s); }
-
-
-// ---- training-mode tower forward / backward (module-level autograd) ------------------------
-// TowerEncoder.forward under autograd (encoders.py:221-255) in two calls: the forward keeps its
-// activations in the workspace, the backward (same tower, rows and workspace) runs the tower's
-// backward kernels — gate, dgrad chain, one grouped weight-gradient launch — into the caller's
-// gradient arena (tower_grad_floats: per Linear weight then bias, 256-B aligned pieces) and
-// writes the ID rows' gradient per position (and, identity feature encoder, the feature rows').
-namespace {
-void plan_tower_train(Arena& ar, const ttamm_tower& T, int64_t n, TowerWs& w) {
-    const int D = out_dim(T);
-    w.role = ROLE_USER;
-    w.R = n;
-    w.idx_own = ar.take<int64_t>(n);
-    for (int l = 0; l + 1 < T.n_linear; ++l) {
-        w.hid[l] = ar.take<float>((size_t)n * T.linear[l].out_features);
-        w.dhid[l] = ar.take<float>((size_t)n * T.linear[l].out_features);
-        if (T.activation != TTAMM_ACT_RELU) {
-            w.pre[l] = ar.take<float>((size_t)n * T.linear[l].out_features);
-            if (T.dropout > 0.f) w.mask[l] = ar.take<uint8_t>((size_t)n * T.linear[l].out_features);
-        }
-    }
-    if (uses_ef(T)) {
-        w.ef = ar.take<float>((size_t)n * efw(T));
-        w.dEF = ar.take<float>((size_t)n * efw(T));
-    } else {
-        w.e = ar.take<float>((size_t)n * D);
-        w.f = ar.take<float>((size_t)n * D);
-    }
-    if (T.fusion == TTAMM_FUSION_GATED) {
-        const int Hg = T.gate[0].out_features;
-        w.z = ar.take<float>((size_t)n * Hg);
-        w.dz = ar.take<float>((size_t)n * Hg);
-        w.g = ar.take<float>((size_t)n * D);
-        w.dq = ar.take<float>((size_t)n * D);
-        const int np = T.matmul_bf16 ? 1 : 3;
-        if (gate16_supported(D, Hg, np)) w.gw16 = ar.take<uint16_t>((size_t)gate16_image_elems(D, Hg, np));
-    }
-    WgradShape shapes[TTAMM_MAX_LINEAR + 2];
-    const int ns = wgrad_shapes(T, n, shapes);
-    int rps[kWgradClasses] = {512, 512, 512, 512};
-    if (ns) wgrad_rows_per_split(shapes, ns, rps);
-    for (int c = 0; c < kWgradClasses; ++c) w.wgrad_rps[c] = rps[c];
-    plan_slabs(ar, T, n, w);
-    if (needs_wpad(T)) w.wpad = ar.take<float>((size_t)T.linear[0].out_features * round4(T.linear[0].in_features));
-    if (T.id.max_norm > 0.0) w.renorm_mark = ar.take<int32_t>(T.id.rows);
-}
-
-int bind_tower_train(const ttamm_tower& T, const int64_t* idx, const int64_t* fidx, int64_t n, void* wsp,
-                     size_t ws_bytes, TowerWs& w) {
-    Arena ar{static_cast<char*>(wsp), ws_bytes, 0, false};
-    plan_tower_train(ar, T, n, w);
-    TTAMM_REQUIRE(ar.ok(), "workspace too small for the training tower forward / backward");
-    w.idx = w.idx_own;
-    w.fidx = fidx == idx ? w.idx_own : fidx;  // caller-gathered feature rows: fidx = null (row r)
-    w.key_split = n;
-    return TTAMM_OK;
-}
-}  // namespace
-
-size_t tower_grad_floats_of(const ttamm_tower& T) { return tower_grad_floats(T); }
-
-size_t tower_train_workspace_size(const ttamm_tower& T, int64_t n) {
-    Arena ar{nullptr, 0, 0, true};
-    TowerWs w;
-    plan_tower_train(ar, T, n, w);
-    return ar.off + 256;
-}
-
-int tower_train_forward(const ttamm_tower& T, const int64_t* idx, const int64_t* fidx, int64_t n,
-                        const uint8_t* const* keep_masks, uint64_t seed, uint64_t counter, float* out, void* wsp,
-                        size_t ws_bytes, hipStream_t s) {
-    const int D = out_dim(T);
-    int rc;
-    if ((rc = validate_tower(T, "tower", D, false))) return rc;
-    if (n <= 0) return TTAMM_OK;
-    TowerWs w;
-    if ((rc = bind_tower_train(T, idx, fidx, n, wsp, ws_bytes, w))) return rc;
-    {  // ids outside the table read row 0 (the Python mirror raises IndexError before calling)
-        StageArgs st;
-        std::memset(&st, 0, sizeof(st));
-        st.seg[st.count++] = StageSeg{idx, w.idx_own, n, T.id.rows};
-        if ((rc = launch_stage_rows(st, s))) return rc;
-    }
-    if (w.renorm_mark) {
-        TTAMM_HIP(hipMemsetAsync(w.renorm_mark, 0, (size_t)T.id.rows * sizeof(int32_t), s));
-        w.renorm_tag = 1;
-    }
-    w.t = out;
-    w.t_ld = D;
-    ttamm_batch bt;
-    std::memset(&bt, 0, sizeof(bt));
-    bt.seed = seed;
-    bt.counter = counter;
-    for (int l = 0; keep_masks && l + 1 < T.n_linear; ++l) bt.user_keep_mask[l] = keep_masks[l];
-    const ttamm_tower* TT[2] = {&T, nullptr};
-    TowerWs* WW[2] = {&w, nullptr};
-    return tower_forward(TT, WW, bt, D, false, s, 1);
-}
-
-int tower_train_backward(const ttamm_tower& T, const int64_t* idx, const int64_t* fidx, int64_t n,
-                         const uint8_t* const* keep_masks, const float* d_out, float* grad_arena, float* d_id_rows,
-                         float* d_feat_rows, void* wsp, size_t ws_bytes, hipStream_t s) {
-    const int D = out_dim(T);
-    const int Did = T.id.dim;
-    int rc;
-    if ((rc = validate_tower(T, "tower", D, false))) return rc;
-    const size_t ng = tower_grad_floats(T);
-    if (n <= 0) {
-        if (ng) TTAMM_HIP(hipMemsetAsync(grad_arena, 0, ng * sizeof(float), s));
-        return TTAMM_OK;
-    }
-    TTAMM_REQUIRE(d_out && (ng == 0 || grad_arena), "tower backward: d_out / grad_arena missing");
-    TowerWs w;
-    if ((rc = bind_tower_train(T, idx, fidx, n, wsp, ws_bytes, w))) return rc;
-    w.dT = d_out;
-    w.dT_ld = D;
-    float* cur = grad_arena;
-    carve_grads(T, w, cur);
-    // non-ReLU layers read the forward's keep bytes: the injected masks again, or the ones the
-    // forward drew into the workspace
-    for (int l = 0; l + 1 < T.n_linear; ++l) w.keep[l] = keep_masks && keep_masks[l] ? keep_masks[l] : w.mask[l];
-    const ttamm_tower* TT[2] = {&T, nullptr};
-    TowerWs* WW[2] = {&w, nullptr};
-    if (T.fusion != TTAMM_FUSION_IDENTITY)
-        if ((rc = tower_backward(TT, WW, D, s, 1))) return rc;
-    // d(ID rows): [e | f] towers take dEF[:, :Did]; sum / identity fusion pass dT to e
-    const float* de = uses_ef(T) ? w.dEF : d_out;
-    const int64_t ld_de = uses_ef(T) ? efw(T) : D;
-    if (d_id_rows && (rc = launch_add_rows(de, ld_de, nullptr, 0, n, Did, d_id_rows, Did, s))) return rc;
-    if (d_feat_rows) {  // identity feature encoder: f = the feature row, its gradient is dEF[:, Did:] / dT
-        TTAMM_REQUIRE(T.n_linear == 0 && T.fusion != TTAMM_FUSION_IDENTITY,
-                      "tower backward: feature-row gradients exist for the identity feature encoder only");
-        const float* df = uses_ef(T) ? w.dEF + Did : d_out;
-        const int fo = fo_dim(T);
-        if ((rc = launch_add_rows(df, ld_de, nullptr, 0, n, fo, d_feat_rows, fo, s))) return rc;
-    }
     return TTAMM_OK;
 }
 
