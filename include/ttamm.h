@@ -384,7 +384,23 @@ typedef struct ttamm_step_args {
     const int64_t* exchange_counts;
     int64_t exchange_counts_ld;
     int32_t exchange_world;
+    /* ---- the in-batch objective (in_batch != 0; zero-filled = the BCE mean above) --------------
+     * TTAMM_INBATCH_BCE:     the BCE mean over every logit of S (and the sampled negatives);
+     * TTAMM_INBATCH_SOFTMAX: the softmax cross-entropy over each user's row of S / temperature,
+     *   L = mean_b( log sum_j exp(S_bj / t) - S_bb / t ), in_batch_inv_temperature = 1 / t.  It
+     *   needs in_batch != 0, b.num_neg == 0 (sampled negatives do not join the denominator), a finite
+     *   positive in_batch_inv_temperature and phase == TTAMM_PHASE_ALL (the row-sharded step is not
+     *   built for it); anything else is TTAMM_E_INVALID.  Two passes, nothing batch x batch stored:
+     *   a row log-sum-exp pass that owns the loss, then the gradient kernel.  loss_out[1] (the
+     *   retrieval slot) carries the softmax mean; the mimic and category-alignment terms, clipping
+     *   and the optimizers are unchanged.  TTAMM_FP32_MFMA=exact and TTAMM_IB_KERNEL=p are not
+     *   honoured under softmax.  ttamm_eval_loss_inbatch honours the same two fields. */
+    int32_t in_batch_loss;
+    float in_batch_inv_temperature;
 } ttamm_step_args;
+
+#define TTAMM_INBATCH_BCE 0
+#define TTAMM_INBATCH_SOFTMAX 1
 
 #define TTAMM_G0_EXACT 0
 #define TTAMM_G0_FAST 1
@@ -736,6 +752,38 @@ size_t ttamm_inbatch_loss_workspace_size(int64_t batch, int64_t n_positives, int
 int ttamm_inbatch_bce_loss(const float* users, int64_t batch, int64_t ldu, const float* positives,
                            int64_t n_positives, int64_t ldp, int32_t dim, int64_t row_base, double* loss_sum,
                            void* workspace, size_t workspace_bytes, void* stream);
+
+/* In-batch softmax cross-entropy as one op: with S = users . positives^T [batch, n_positives] and
+ * user b's own positive at column row_base + b,
+ *   lse_b     = log sum_j exp(S_bj * inv_temperature)              (j over all n_positives columns)
+ *   *loss_sum = sum_b (lse_b - S_{b,row_base+b} * inv_temperature) (fp64 on the device)
+ *   dS_bj     = (exp(S_bj * inv_temperature - lse_b) - [j == row_base + b]) * inv_count * inv_temperature
+ *   d_users = dS . positives, d_positives = dS^T . users.
+ * No duplicate-item masking and no logQ correction.  Nothing batch x n_positives is stored: a row
+ * log-sum-exp pass (running maximum and rescaled sum per row and column split, merged in split
+ * order) writes the loss and each row's (maximum, 1 / sum), from which inbatch_x_kernel's softmax
+ * instantiation forms dS: exp(S_bj * inv_temperature - lse_b) as exp(.. - maximum) / sum.
+ *   read:     every argument; rows must be 16-byte aligned (ldu, ldp multiples of 4).
+ *   written:  d_users [batch, ld_du], d_positives [n_positives, ld_dp], *loss_sum.
+ *   rejected: what ttamm_inbatch_bce rejects, and an inv_temperature that is not finite or <= 0
+ *             (TTAMM_E_INVALID, before any device work).
+ * Every sum has a fixed order (no float atomics): the same inputs give the same bits.  Always the
+ * split-bf16 kernels: TTAMM_FP32_MFMA=exact and TTAMM_IB_KERNEL=p are not honoured. */
+size_t ttamm_inbatch_softmax_workspace_size(int64_t batch, int64_t n_positives, int32_t dim);
+int ttamm_inbatch_softmax(const float* users, int64_t batch, int64_t ldu, const float* positives,
+                          int64_t n_positives, int64_t ldp, int32_t dim, int64_t row_base, float inv_count,
+                          float inv_temperature, float* d_users, int64_t ld_du, float* d_positives,
+                          int64_t ld_dp, double* loss_sum, void* workspace, size_t workspace_bytes,
+                          void* stream);
+
+/* *loss_sum of ttamm_inbatch_softmax alone: the log-sum-exp pass only (the validation kernel); the
+ * same bits as the training op's *loss_sum.  Rejections as ttamm_inbatch_bce_loss, plus
+ * inv_temperature not finite or <= 0. */
+size_t ttamm_inbatch_softmax_loss_workspace_size(int64_t batch, int64_t n_positives, int32_t dim);
+int ttamm_inbatch_softmax_loss(const float* users, int64_t batch, int64_t ldu, const float* positives,
+                               int64_t n_positives, int64_t ldp, int32_t dim, int64_t row_base,
+                               float inv_temperature, double* loss_sum, void* workspace,
+                               size_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }

@@ -374,3 +374,34 @@ TTAMM_API int ttamm_inbatch_bce_loss(const float* users, int64_t batch, int64_t 
     return inbatch_loss_standalone(users, batch, ldu, positives, n_positives, ldp, dim, row_base, loss_sum, workspace,
                                    workspace_bytes, (hipStream_t)stream);
 }
+
+TTAMM_API size_t ttamm_inbatch_softmax_workspace_size(int64_t batch, int64_t n_positives, int32_t dim) {
+    if (batch <= 0 || n_positives <= 0 || dim <= 0) return 0;
+    return inbatch_softmax_workspace_bytes(batch, n_positives, dim);
+}
+
+TTAMM_API int ttamm_inbatch_softmax(const float* users, int64_t batch, int64_t ldu, const float* positives,
+                                    int64_t n_positives, int64_t ldp, int32_t dim, int64_t row_base, float inv_count,
+                                    float inv_temperature, float* d_users, int64_t ld_du, float* d_positives,
+                                    int64_t ld_dp, double* loss_sum, void* workspace, size_t workspace_bytes,
+                                    void* stream) {
+    g_last_error.clear();
+    return inbatch_softmax_standalone(users, batch, ldu, positives, n_positives, ldp, dim, row_base, inv_count,
+                                      inv_temperature, d_users, ld_du, d_positives, ld_dp, loss_sum, workspace,
+                                      workspace_bytes, (hipStream_t)stream);
+}
+
+TTAMM_API size_t ttamm_inbatch_softmax_loss_workspace_size(int64_t batch, int64_t n_positives, int32_t dim) {
+    if (batch <= 0 || n_positives <= 0 || dim <= 0) return 0;
+    return inbatch_softmax_loss_workspace_bytes(batch, n_positives, dim);
+}
+
+TTAMM_API int ttamm_inbatch_softmax_loss(const float* users, int64_t batch, int64_t ldu, const float* positives,
+                                         int64_t n_positives, int64_t ldp, int32_t dim, int64_t row_base,
+                                         float inv_temperature, double* loss_sum, void* workspace,
+                                         size_t workspace_bytes, void* stream) {
+    g_last_error.clear();
+    return inbatch_softmax_loss_standalone(users, batch, ldu, positives, n_positives, ldp, dim, row_base,
+                                           inv_temperature, loss_sum, workspace, workspace_bytes,
+                                           (hipStream_t)stream);
+}

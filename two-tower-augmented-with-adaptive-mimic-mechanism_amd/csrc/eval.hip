@@ -71,6 +71,7 @@ struct EvalWs {
     int blocks = 0;
     float* ib_partials = nullptr;  // in-batch pass: inbatch_loss_kernel's block sums
     int ib_blocks = 0;
+    InBatchLossArgs ib_lse{};      // in-batch softmax: the LSE pass (in_batch_loss)
 };
 
 // Forward buffers for B and B(1+N) rows, the staged ids, the weight pads / images the forward
@@ -90,7 +91,11 @@ void plan_eval(Arena& ar, const ttamm_step_args& A, EvalWs& ws, bool in_batch = 
     plan_tower(ar, A.item, B * (1 + (int64_t)N), o, ws.item);
     ws.blocks = score_blocks(B, D);
     ws.partials = ar.take<float>((size_t)ws.blocks);
-    if (in_batch) {
+    if (in_batch && A.in_batch_loss == TTAMM_INBATCH_SOFTMAX) {  // the LSE pass's workspace
+        ws.ib_lse.B = ws.ib_lse.Bc = B;
+        float* w = ar.take<float>(inbatch_lse_floats(B, B));
+        if (!ar.measuring) inbatch_lse_bind(ws.ib_lse, w);
+    } else if (in_batch) {
         ws.ib_blocks = inbatch_loss_blocks(B, B);
         ws.ib_partials = ar.take<float>((size_t)ws.ib_blocks);
     }
@@ -105,6 +110,14 @@ int validate_eval(const ttamm_step_args& A, bool in_batch = false) {
         TTAMM_REQUIRE(A.b.num_neg >= 0 && A.b.num_neg <= 64,
                       "eval loss (in-batch): b.num_neg (negatives_per_positive) must be in [0, 64]");
         if ((rc = inbatch_loss_check(D))) return rc;
+        TTAMM_REQUIRE(A.in_batch_loss == TTAMM_INBATCH_BCE || A.in_batch_loss == TTAMM_INBATCH_SOFTMAX,
+                      "in_batch_loss must be 0 (the BCE mean) or 1 (the softmax cross-entropy)");
+        if (A.in_batch_loss == TTAMM_INBATCH_SOFTMAX) {
+            TTAMM_REQUIRE(A.b.num_neg == 0,
+                          "in_batch_loss: the softmax objective needs b.num_neg == 0 (sampled negatives do not join "
+                          "the denominator)");
+            if ((rc = inbatch_softmax_check(A.in_batch_inv_temperature))) return rc;
+        }
     } else {
         TTAMM_REQUIRE(A.in_batch == 0, "eval loss: in_batch must be 0 (_compute_loss scores sampled negatives only)");
         if ((rc = score_eval_check(A.b.num_neg, D))) return rc;
@@ -180,6 +193,13 @@ static int eval_loss_run(const ttamm_step_args& A, float* logits_out, bool in_ba
     sa.partials = ws.partials;
     sa.blocks = ws.blocks;
     sa.logits = logits_out;
+    if (in_batch && A.in_batch_loss == TTAMM_INBATCH_SOFTMAX) {  // one LSE pass, the mean of its B terms
+        InBatchLossArgs& l = ws.ib_lse;
+        l.U = U.aug, l.ldu = D, l.P = I.aug, l.ldp = D, l.D = D, l.row_base = 0;
+        if ((rc = launch_inbatch_lse(l, A.in_batch_inv_temperature, s))) return rc;
+        return launch_eval_loss_inbatch_finalize(nullptr, 0, l.loss_part, inbatch_lse_parts(B), B, B, A.loss_out,
+                                                 A.loss_accum, A.status, s);
+    }
     if (in_batch) {
         InBatchLossArgs ib{};
         ib.U = U.aug, ib.ldu = D, ib.B = B, ib.P = I.aug, ib.ldp = D, ib.Bc = B, ib.D = D;

@@ -15,7 +15,16 @@
 // its LDS slice and multiplies it back against the same LDS tile (K = 64).  Blocks write
 // partial rows to slabs that ib_reduce_kernel sums in split order (deterministic).  This fp32-MFMA
 // kernel runs with TTAMM_FP32_MFMA=exact; the default is the split-bf16 inbatch_x_kernel below.
+//
+// The softmax objective (ttamm.h in_batch_loss, ttamm_inbatch_softmax): the cross-entropy over each
+// user's row of S / temperature, in two passes — inbatch_loss_kernel's softmax form (row
+// log-sum-exp per column split) and ib_lse_merge_kernel own lse, the loss and the rows'
+// (maximum, 1 / sum), then inbatch_x_kernel's softmax instantiation forms
+// dS = (exp(S / t - max) / sum - Y) inv_count / t = (exp(S / t - lse) - Y) inv_count / t.  Only
+// inbatch_x_kernel has a softmax form: under softmax launch_inbatch_softmax ignores
+// TTAMM_FP32_MFMA=exact and TTAMM_IB_KERNEL=p (as the forward-only BCE op ignores the former).
 #include <algorithm>
+#include <cmath>
 #include <cstdlib>
 #include <cstring>
 
@@ -239,31 +248,57 @@ __device__ __forceinline__ bf16x8_t ibx_cat(uint2 a, uint2 b) {
 #ifndef TTAMM_IB_PRODUCTS
 #define TTAMM_IB_PRODUCTS 5
 #endif
+template <int NP = TTAMM_IB_PRODUCTS>
 __device__ __forceinline__ f32x16 ibx_mfma6(const bf16x8_t a[3], const bf16x8_t b[3], f32x16 c) {
     c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], b[0], c, 0, 0, 0);
     c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], b[1], c, 0, 0, 0);
     c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[1], b[0], c, 0, 0, 0);
-    if constexpr (TTAMM_IB_PRODUCTS == 6 || TTAMM_IB_PRODUCTS == 5) {
+    if constexpr (NP == 6 || NP == 5) {
         c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], b[2], c, 0, 0, 0);
         c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[2], b[0], c, 0, 0, 0);
     }
-    if constexpr (TTAMM_IB_PRODUCTS == 6 || TTAMM_IB_PRODUCTS == 4)
+    if constexpr (NP == 6 || NP == 4)
         c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[1], b[1], c, 0, 0, 0);
     return c;
 }
+// The softmax instantiations (the LSE pass, both products of the gradient kernel) keep all 6: a
+// row's gradient is dominated by its own positive's term instead of averaging over the row, and
+// the logit error is multiplied by 1 / temperature in the exponent, so mm (<= 2^-18 relative)
+// shows.  Against the float64 definition (profiles/inbatch_softmax_products.txt), 5 -> 6 products:
+// t = 1, 300 x 300 x 96: dU 7.7e-6 -> 4.5e-7, dP 6.8e-6 -> 4.8e-7; t = 0.25: dP 1.0e-5 -> 3.1e-6;
+// t = 0.02 (200 x 900 x 64): dU 5.8e-5 -> 5.9e-6 (float32 torch: 7.5e-6), for 1.18x -> 1.31x the BCE
+// op's time at 8192 x 8192 x 96.  The sixth product in the score product of the gradient kernel
+// alone is worse than none (t = 0.25: 3.4e-5): p = exp(z - lse) needs z and lse from one S.
+#ifndef TTAMM_IB_SOFTMAX_PRODUCTS
+#define TTAMM_IB_SOFTMAX_PRODUCTS 6
+#endif
 
 // MINB blocks per CU of NW waves (32 rows each); DBUF: two LDS tile buffers (one barrier per
-// tile, the next tile split and stored right after this one's MFMAs)
-template <int DP, int MINB, int NW, bool DBUF>
+// tile, the next tile split and stored right after this one's MFMAs).
+// LOSS (compile time; the BCE code is the same with or without the softmax branch):
+//   TTAMM_INBATCH_BCE      dS = (sigmoid(S) - Y) * inv_T, the BCE terms summed into loss_part;
+//   TTAMM_INBATCH_SOFTMAX  dS = (exp2(S * z_scale - rmax) * rinv - Y) * inv_T with the rows' (rmax,
+//     rinv) = (maximum, 1 / sum; log2 units) from the LSE pass: the user role keeps its row's pair in
+//     two registers, the item role (register index = user) stages the tile's 64 users' pairs next
+//     to the tile and reads them as float4 (registers r & 3 of one r >> 2 group are four
+//     consecutive tile columns; every lane of a half wave reads one address: a broadcast).  inv_T
+//     multiplies the accumulators once at the slab write, not every element.  No loss is
+//     accumulated: the LSE pass owns it.
+template <int DP, int MINB, int NW, bool DBUF, int LOSS = TTAMM_INBATCH_BCE>
 __global__ __launch_bounds__(64 * NW, MINB) void inbatch_x_kernel(InBatchArgs A) {
     constexpr int NT = 64 * NW;                      // threads
     constexpr int NB = DP / 32;                      // 32-wide output column blocks
     constexpr int KS = DP / 16;                      // k steps of product 1
     constexpr int TF4 = kIbTile * DP / 4;            // float4 per column tile
     constexpr int LOADS = TF4 / NT;
+    constexpr bool SOFTMAX = LOSS == TTAMM_INBATCH_SOFTMAX;
+    constexpr int NP = SOFTMAX ? TTAMM_IB_SOFTMAX_PRODUCTS : TTAMM_IB_PRODUCTS;  // partial products
     static_assert(TF4 % NT == 0, "whole staging rounds");
+    static_assert(NT >= 2 * kIbTile, "one thread per staged rmax / rinv");
     __shared__ __attribute__((aligned(16))) unsigned char tiles[DBUF ? 2 : 1][3 * kIbxPlane];
     __shared__ float red[NW];
+    // [buffer][rmax | rinv][tile column]
+    __shared__ __attribute__((aligned(16))) float nrm_t[SOFTMAX ? (DBUF ? 2 : 1) : 1][2][SOFTMAX ? kIbTile : 2];
 
     int blk = blockIdx.x;
     const int nu = A.rblk_u * A.splits_u;
@@ -331,6 +366,24 @@ __global__ __launch_bounds__(64 * NW, MINB) void inbatch_x_kernel(InBatchArgs A)
             for (int q = 0; q < 3; ++q) *reinterpret_cast<uint2*>(dst + q * kIbxPlane + o) = pl[q];
         }
     };
+    // softmax: the user role's row (rmax, rinv) in two registers; the item role's tile columns are
+    // users, whose pairs travel with the tile (threads 0..63 rmax, 64..127 rinv; zero past c_end:
+    // those elements are masked)
+    const int64_t gr = r0 + li;
+    float max_r = 0.f, inv_r = 0.f, st_l = 0.f;
+    if constexpr (SOFTMAX)
+        if (role_u && gr < nr) max_r = A.rmax[gr], inv_r = A.rinv[gr];
+    auto load_lse = [&](int64_t c0) {
+        if constexpr (SOFTMAX)
+            if (!role_u && tid < 2 * kIbTile) {
+                const int64_t u = c0 + (tid & (kIbTile - 1));
+                st_l = u < c_end ? (tid < kIbTile ? A.rmax[u] : A.rinv[u]) : 0.f;
+            }
+    };
+    auto store_lse = [&](int buf) {
+        if constexpr (SOFTMAX)
+            if (!role_u && tid < 2 * kIbTile) nrm_t[buf][tid >> 6][tid & (kIbTile - 1)] = st_l;
+    };
 
     const int ntiles = c_end > c_begin ? (int)((c_end - c_begin + kIbTile - 1) / kIbTile) : 0;
     // the next tile in flight in registers while this one is multiplied (narrow D); at D > 64 the
@@ -339,25 +392,37 @@ __global__ __launch_bounds__(64 * NW, MINB) void inbatch_x_kernel(InBatchArgs A)
     if (DBUF) {  // tile 0 in buffer 0, tile 1 in flight in registers
         if (ntiles > 0) {
             load(c_begin);
+            load_lse(c_begin);
             store(tiles[0]);
-            if (ntiles > 1) load(c_begin + kIbTile);
+            store_lse(0);
+            if (ntiles > 1) {
+                load(c_begin + kIbTile);
+                load_lse(c_begin + kIbTile);
+            }
         }
         __syncthreads();
     } else if (PREFETCH && ntiles > 0) {
         load(c_begin);
+        load_lse(c_begin);
     }
     // tr-read lane roles: 16-lane group g, lane 4q + p of the group
     const int g = lane >> 4, q4 = (lane >> 2) & 3, p4 = lane & 3;
-    const int64_t gr = r0 + li;
     for (int t = 0; t < ntiles; ++t) {
         const int64_t c0 = c_begin + (int64_t)t * kIbTile;
         unsigned char* const tile = tiles[DBUF ? (t & 1) : 0];
         if (!DBUF) {
-            if (!PREFETCH) load(c0);
+            if (!PREFETCH) {
+                load(c0);
+                load_lse(c0);
+            }
             __syncthreads();  // every wave is done with the previous tile
             store(tile);
+            store_lse(0);
             __syncthreads();
-            if (PREFETCH && t + 1 < ntiles) load(c0 + kIbTile);  // in flight during this tile's MFMAs
+            if (PREFETCH && t + 1 < ntiles) {  // in flight during this tile's MFMAs
+                load(c0 + kIbTile);
+                load_lse(c0 + kIbTile);
+            }
         }
         // the label Y = 1 sits at tile column diag of this lane's row: user u's own positive is
         // column row_base + u (user role), positive i's user is row i - row_base (item role)
@@ -379,14 +444,44 @@ __global__ __launch_bounds__(64 * NW, MINB) void inbatch_x_kernel(InBatchArgs A)
                 bf16x8_t a[3];
 #pragma unroll
                 for (int q = 0; q < 3; ++q) a[q] = *reinterpret_cast<const bf16x8_t*>(tile + q * kIbxPlane + o);
-                s2 = ibx_mfma6(a, rf[s], s2);
+                s2 = ibx_mfma6<NP>(a, rf[s], s2);
             }
             // ---- dS^T in registers (lane: row u = r0 + li; register r: tile column c) -----------
             // hardware exp2 / log2 / rcp (<= 1-2 ulp): this elementwise pass, not the MFMAs, bounds
             // the kernel with IEEE expf / logf / division.  Sigmoid and the ATen BCE term from one
             // exp: t = exp(-|x|); for x >= 0 exp(-max(-x,0)) = 1 and exp(-x-max(-x,0)) = t, for x < 0
             // the reverse.
-            if (fast) {
+            if constexpr (SOFTMAX) {
+                // softmax: p = exp2(x z_scale - rmax) rinv (one fma, one hardware exp2, one multiply),
+                // dS / inv_T = p - y; the interior fast path has no y and no range tests
+                const float zc = A.z_scale;
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {  // registers 4 q .. 4 q + 3: four consecutive tile columns
+                    float4 m4, i4;
+                    if (!role_u) {
+                        const float* nt = nrm_t[DBUF ? (t & 1) : 0][0] + 32 * jc + 4 * h + 8 * q;
+                        m4 = *reinterpret_cast<const float4*>(nt);
+                        i4 = *reinterpret_cast<const float4*>(nt + (SOFTMAX ? kIbTile : 2));
+                    } else {
+                        m4 = make_float4(max_r, max_r, max_r, max_r);
+                        i4 = make_float4(inv_r, inv_r, inv_r, inv_r);
+                    }
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) {
+                        const int r = 4 * q + e;
+                        s2[r] = __builtin_amdgcn_exp2f(__builtin_fmaf(s2[r], zc, -f4at(m4, e))) * f4at(i4, e);
+                    }
+                }
+                if (!fast) {
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) {
+                        const int lc = 32 * jc + (r & 3) + 8 * (r >> 2) + 4 * h;
+                        const bool ok = row_ok && lc < cols_here;
+                        const float y = lc == diag ? 1.0f : 0.0f;
+                        s2[r] = ok ? s2[r] - y : 0.f;
+                    }
+                }
+            } else if (fast) {
                 // every row and column in range, no label in this wave's block: y = 0, so the BCE
                 // term is max(x, 0) + ln(1 + t) (x + max(-x, 0) == max(x, 0) exactly), summed as
                 // two lane sums (the log2 terms scaled by ln 2 once at the end)
@@ -453,7 +548,7 @@ __global__ __launch_bounds__(64 * NW, MINB) void inbatch_x_kernel(InBatchArgs A)
                         const s16x8_t v = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
                         b[q] = __builtin_bit_cast(bf16x8_t, v);
                     }
-                    acc[n] = ibx_mfma6(a, b, acc[n]);
+                    acc[n] = ibx_mfma6<NP>(a, b, acc[n]);
                 }
             }
         }
@@ -462,7 +557,11 @@ __global__ __launch_bounds__(64 * NW, MINB) void inbatch_x_kernel(InBatchArgs A)
             // read in tile t - 1 before that tile's barrier; tile t + 2 in flight
             if (t + 1 < ntiles) {
                 store(tiles[(t + 1) & 1]);
-                if (t + 2 < ntiles) load(c0 + 2 * kIbTile);
+                store_lse((t + 1) & 1);
+                if (t + 2 < ntiles) {
+                    load(c0 + 2 * kIbTile);
+                    load_lse(c0 + 2 * kIbTile);
+                }
             }
             __syncthreads();
         }
@@ -476,9 +575,9 @@ __global__ __launch_bounds__(64 * NW, MINB) void inbatch_x_kernel(InBatchArgs A)
             const int lr = (r & 3) + 8 * (r >> 2) + 4 * h;
             const int64_t gr = r0 + lr;
             const int col = 32 * n + li;
-            if (gr < nr && col < D) slab[gr * D + col] = acc[n][r];
+            if (gr < nr && col < D) slab[gr * D + col] = SOFTMAX ? acc[n][r] * A.inv_T : acc[n][r];
         }
-    if (role_u) {
+    if (!SOFTMAX && role_u) {
         bce = wave_sum(bce + (bce_lin + bce_log2 * 0.6931471805599453f));
         if (lane == 0) red[w] = bce;
         __syncthreads();
@@ -830,8 +929,20 @@ constexpr int kIblWaves = 8;
 constexpr int kIblRows = 32 * kIblWaves;
 constexpr int kIblBlocks = 256;  // one resident round: a block per CU
 
-template <int DP>
+//
+// LOSS == TTAMM_INBATCH_SOFTMAX is the row log-sum-exp pass of the softmax loss over the same
+// structure: instead of BCE terms a lane keeps, in log2 units (z = S * z_scale, z_scale =
+// log2(e) / temperature), the running maximum m of its row's columns and the sum of exp2(z - m),
+// rescaled when a tile raises m; only in-range elements enter (columns past c_end and rows past B
+// are excluded, not added as zeros).  A row lives on lanes li and li + 32 (different columns): the
+// halves are joined, then the block writes one (m, sum) pair per row into its split's plane of ms
+// and, in the split whose columns hold it, the row's own positive's z into zpos.
+// ib_lse_merge_kernel finishes the rows.
+constexpr float kIbNegBig = -3.0e38f;  // "no column yet": finite, so m - m stays 0 and not NaN
+
+template <int DP, int LOSS = TTAMM_INBATCH_BCE>
 __global__ __launch_bounds__(64 * kIblWaves, 1) void inbatch_loss_kernel(InBatchLossArgs A) {
+    constexpr bool SOFTMAX = LOSS == TTAMM_INBATCH_SOFTMAX;
     constexpr int NT = 64 * kIblWaves;
     constexpr int KS = DP / 16;            // k steps of the score product
     constexpr int TF4 = kIbTile * DP / 4;  // float4 per column tile
@@ -870,6 +981,7 @@ __global__ __launch_bounds__(64 * kIblWaves, 1) void inbatch_loss_kernel(InBatch
         }
     }
     float bce = 0.f, bce_lin = 0.f, bce_log2 = 0.f;
+    float m_run = kIbNegBig, s_run = 0.f, z_pos = kIbNegBig;  // softmax: this lane's columns of its row
 
     // column tile -> registers (zero past c_end / D) -> the three planes of an LDS image
     float4 st[LOADS];
@@ -926,9 +1038,39 @@ __global__ __launch_bounds__(64 * kIblWaves, 1) void inbatch_loss_kernel(InBatch
                 bf16x8_t a[3];
 #pragma unroll
                 for (int q = 0; q < 3; ++q) a[q] = *reinterpret_cast<const bf16x8_t*>(tile + q * kIbxPlane + o);
-                s2 = ibx_mfma6(a, rf[s], s2);
+                s2 = ibx_mfma6<SOFTMAX ? TTAMM_IB_SOFTMAX_PRODUCTS : TTAMM_IB_PRODUCTS>(a, rf[s], s2);
             }
-            if (fast) {
+            if constexpr (SOFTMAX) {
+                // online log-sum-exp of these 16 columns: z_scale > 0, so max z = z_scale max x
+                const float zc = A.z_scale;
+                float mx = kIbNegBig;
+                if (fast) {
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) mx = fmaxf(mx, s2[r]);
+                } else {
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) {
+                        const int lc = 32 * jc + (r & 3) + 8 * (r >> 2) + 4 * h;
+                        if (row_ok && lc < cols_here) mx = fmaxf(mx, s2[r]);
+                        if (row_ok && lc == diag) z_pos = s2[r] * zc;
+                    }
+                }
+                const float m_new = fmaxf(m_run, mx > kIbNegBig ? mx * zc : kIbNegBig);
+                float add = 0.f;
+                if (fast) {
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) add += __builtin_amdgcn_exp2f(__builtin_fmaf(s2[r], zc, -m_new));
+                } else {
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) {
+                        const int lc = 32 * jc + (r & 3) + 8 * (r >> 2) + 4 * h;
+                        const float e = __builtin_amdgcn_exp2f(__builtin_fmaf(s2[r], zc, -m_new));
+                        add += (row_ok && lc < cols_here) ? e : 0.f;
+                    }
+                }
+                s_run = s_run * __builtin_amdgcn_exp2f(m_run - m_new) + add;
+                m_run = m_new;
+            } else if (fast) {
                 // y = 0 everywhere: the term is max(x, 0) + ln(1 + t), t = exp(-|x|), summed as two
                 // lane sums (the log2 terms scaled by ln 2 once at the end)
 #pragma unroll
@@ -958,15 +1100,64 @@ __global__ __launch_bounds__(64 * kIblWaves, 1) void inbatch_loss_kernel(InBatch
         }
         __syncthreads();
     }
-    bce = wave_sum(bce + (bce_lin + bce_log2 * 0.6931471805599453f));
-    if (lane == 0) red[w] = bce;
-    __syncthreads();
-    if (tid == 0) {
-        float sum = 0.f;
+    if constexpr (SOFTMAX) {
+        // join the row's two half-wave lanes (h = 0 writes), then one pair per row and split
+        const float m_o = __shfl_xor(m_run, 32, 64), s_o = __shfl_xor(s_run, 32, 64), z_o = __shfl_xor(z_pos, 32, 64);
+        const float m = fmaxf(m_run, m_o);
+        const float sum = s_run * __builtin_amdgcn_exp2f(m_run - m) + s_o * __builtin_amdgcn_exp2f(m_o - m);
+        const float zp = fmaxf(z_pos, z_o);
+        if (h == 0 && row_ok) {
+            *reinterpret_cast<float2*>(A.ms + 2 * ((int64_t)sp * A.B + gr)) = make_float2(m, sum);
+            const int64_t pc = A.row_base + gr;  // the row's own positive: in exactly one split
+            if (pc >= c_begin && pc < c_end) A.zpos[gr] = zp;
+        }
+    } else {
+        bce = wave_sum(bce + (bce_lin + bce_log2 * 0.6931471805599453f));
+        if (lane == 0) red[w] = bce;
+        __syncthreads();
+        if (tid == 0) {
+            float sum = 0.f;
 #pragma unroll
-        for (int i = 0; i < kIblWaves; i += 2) sum += red[i] + red[i + 1];
-        A.loss_part[blk] = sum;
+            for (int i = 0; i < kIblWaves; i += 2) sum += red[i] + red[i + 1];
+            A.loss_part[blk] = sum;
+        }
     }
+}
+
+// The rows' splits merged in split order: lse[b] = m + log2(sum) (log2 units), term[b] =
+// (lse[b] - zpos[b]) ln 2 = lse_b - S_bb / temperature, and the terms of a block's 256 rows summed
+// by a fixed tree into loss_part[block].  No float atomics.  The gradient kernel gets the pair
+// (rmax, rinv) = (m, 1 / sum) and not lse: p = exp2(z - m) / sum leaves a row of p summing to 1
+// within the rounding of sum (about 6e-8), while one float lse of magnitude log2 Bc + max z carries
+// half an ulp of its own (2e-7 to 5e-7) into every p of the row, and the sums over the batch that
+// cancel under softmax (sum_j dP_j = sum_b (sum_j dS_bj) U_b) multiply exactly that.
+__global__ __launch_bounds__(256) void ib_lse_merge_kernel(InBatchLossArgs A) {
+    __shared__ float red[256];
+    const int64_t b = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    float term = 0.f;
+    if (b < A.B) {
+        float2 v = *reinterpret_cast<const float2*>(A.ms + 2 * b);
+        float m = v.x, sum = v.y;
+        for (int k = 1; k < A.splits; ++k) {
+            v = *reinterpret_cast<const float2*>(A.ms + 2 * ((int64_t)k * A.B + b));
+            const float mn = fmaxf(m, v.x);
+            sum = sum * exp2f(m - mn) + v.y * exp2f(v.x - mn);
+            m = mn;
+        }
+        const float l = m + log2f(sum);
+        term = (l - A.zpos[b]) * 0.6931471805599453f;
+        A.lse[b] = l;
+        A.term[b] = term;
+        A.rmax[b] = m;
+        A.rinv[b] = 1.0f / sum;  // the maximum's own term is 1: never a division by zero
+    }
+    red[threadIdx.x] = term;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) A.loss_part[blockIdx.x] = red[0];
 }
 
 }  // namespace
@@ -1024,11 +1215,26 @@ size_t inbatch_workspace_floats(int64_t B, int64_t Bc, int D, size_t* slab_u, si
     return *slab_u + *slab_p + *parts;
 }
 
-int launch_inbatch(InBatchArgs& a, hipStream_t s) {
+static int inbatch_check(const InBatchArgs& a) {
     TTAMM_REQUIRE(a.D > 0 && a.D % 4 == 0 && a.D <= 128, "in-batch negatives: embedding dim must be a multiple of 4, <= 128");
     TTAMM_REQUIRE(a.B > 0 && a.Bc > 0 && a.B < (int64_t(1) << 31) && a.Bc < (int64_t(1) << 31), "in-batch: bad batch");
     TTAMM_REQUIRE(a.ldu % 4 == 0 && a.ldp % 4 == 0 && ((uintptr_t)a.U | (uintptr_t)a.P) % 16 == 0,
                   "in-batch: rows must be 16-byte aligned");
+    return TTAMM_OK;
+}
+
+// dU / dP = the slabs summed in split order
+static int launch_inbatch_reduce(const InBatchArgs& a, hipStream_t s) {
+    const int64_t total = (a.B + a.Bc) * a.D;
+    hipLaunchKernelGGL(ib_reduce_kernel, dim3((unsigned)std::min<int64_t>(ceil_div(total, 256), 8192)), dim3(256), 0, s,
+                       a);
+    TTAMM_LAUNCH_CHECK();
+    return TTAMM_OK;
+}
+
+int launch_inbatch(InBatchArgs& a, hipStream_t s) {
+    int rc;
+    if ((rc = inbatch_check(a))) return rc;
     inbatch_plan(a.B, a.Bc, a);
     const unsigned blocks = (unsigned)(a.rblk_u * a.splits_u + a.rblk_p * a.splits_p);
     const int dp = (a.D + 31) / 32 * 32;
@@ -1081,11 +1287,7 @@ int launch_inbatch(InBatchArgs& a, hipStream_t s) {
         }
     }
     TTAMM_LAUNCH_CHECK();
-    const int64_t total = (a.B + a.Bc) * a.D;
-    hipLaunchKernelGGL(ib_reduce_kernel, dim3((unsigned)std::min<int64_t>(ceil_div(total, 256), 8192)), dim3(256), 0, s,
-                       a);
-    TTAMM_LAUNCH_CHECK();
-    return TTAMM_OK;
+    return launch_inbatch_reduce(a, s);
 }
 
 size_t inbatch_standalone_workspace_bytes(int64_t B, int64_t Bc, int D) {
@@ -1163,6 +1365,153 @@ int launch_inbatch_loss(InBatchLossArgs& a, hipStream_t s) {
 size_t inbatch_loss_workspace_bytes(int64_t B, int64_t Bc, int D) {
     (void)D;
     return sizeof(float) * (size_t)inbatch_loss_blocks(B, Bc);
+}
+
+// ---- in-batch softmax: the LSE pass, then inbatch_x_kernel's softmax instantiation -----------------
+// The LSE pass runs on inbatch_loss_plan's blocks (a function of the shapes only); its workspace is
+// [ms: splits x B pairs | zpos B | lse B | term B | rmax B | rinv B | loss_part: one float per 256 rows].
+int inbatch_lse_parts(int64_t B) { return (int)ceil_div(B, 256); }
+
+size_t inbatch_lse_floats(int64_t B, int64_t Bc) {
+    InBatchLossArgs a{};
+    inbatch_loss_plan(B, Bc, a);
+    return 2 * (size_t)a.splits * B + 5 * (size_t)B + (size_t)inbatch_lse_parts(B);
+}
+
+void inbatch_lse_bind(InBatchLossArgs& a, float* w) {
+    inbatch_loss_plan(a.B, a.Bc, a);
+    a.ms = w;  // even offsets: the pairs are read and written as float2
+    a.zpos = a.ms + 2 * (size_t)a.splits * a.B;
+    a.lse = a.zpos + a.B;
+    a.term = a.lse + a.B;
+    a.rmax = a.term + a.B;
+    a.rinv = a.rmax + a.B;
+    a.loss_part = a.rinv + a.B;
+}
+
+int inbatch_softmax_check(float inv_temperature) {
+    TTAMM_REQUIRE(std::isfinite(inv_temperature) && inv_temperature > 0.f,
+                  "in-batch softmax: the inverse temperature must be finite and greater than zero");
+    return TTAMM_OK;
+}
+
+int launch_inbatch_lse(InBatchLossArgs& a, float inv_temperature, hipStream_t s) {
+    int rc;
+    if ((rc = inbatch_loss_check(a.D))) return rc;
+    if ((rc = inbatch_softmax_check(inv_temperature))) return rc;
+    TTAMM_REQUIRE(a.B > 0 && a.Bc > 0 && a.B < (int64_t(1) << 31) && a.Bc < (int64_t(1) << 31), "in-batch: bad batch");
+    TTAMM_REQUIRE(a.ldu % 4 == 0 && a.ldp % 4 == 0 && ((uintptr_t)a.U | (uintptr_t)a.P) % 16 == 0,
+                  "in-batch: rows must be 16-byte aligned");
+    TTAMM_REQUIRE(a.row_base >= 0 && a.row_base + a.B <= a.Bc, "in-batch: the users' labels must lie inside the columns");
+    TTAMM_REQUIRE(a.ms && a.zpos && a.lse && a.term && a.rmax && a.rinv && a.loss_part && (uintptr_t)a.ms % 8 == 0,
+                  "in-batch softmax: LSE workspace not bound");
+    inbatch_loss_plan(a.B, a.Bc, a);
+    a.z_scale = inv_temperature * 1.4426950408889634f;
+    const dim3 g((unsigned)(a.rblk * a.splits)), t(64 * kIblWaves);
+    switch ((a.D + 31) / 32 * 32) {
+        case 32: hipLaunchKernelGGL((inbatch_loss_kernel<32, TTAMM_INBATCH_SOFTMAX>), g, t, 0, s, a); break;
+        case 64: hipLaunchKernelGGL((inbatch_loss_kernel<64, TTAMM_INBATCH_SOFTMAX>), g, t, 0, s, a); break;
+        case 96: hipLaunchKernelGGL((inbatch_loss_kernel<96, TTAMM_INBATCH_SOFTMAX>), g, t, 0, s, a); break;
+        default: hipLaunchKernelGGL((inbatch_loss_kernel<128, TTAMM_INBATCH_SOFTMAX>), g, t, 0, s, a); break;
+    }
+    TTAMM_LAUNCH_CHECK();
+    hipLaunchKernelGGL(ib_lse_merge_kernel, dim3((unsigned)inbatch_lse_parts(a.B)), dim3(256), 0, s, a);
+    TTAMM_LAUNCH_CHECK();
+    return TTAMM_OK;
+}
+
+int launch_inbatch_softmax(InBatchArgs& a, InBatchLossArgs& l, float inv_temperature, hipStream_t s) {
+    int rc;
+    if ((rc = inbatch_check(a))) return rc;
+    if ((rc = launch_inbatch_lse(l, inv_temperature, s))) return rc;
+    a.rmax = l.rmax, a.rinv = l.rinv;
+    a.z_scale = l.z_scale;
+    a.inv_T *= inv_temperature;  // dS = (p - y) inv_count / temperature
+    inbatch_plan(a.B, a.Bc, a);
+    const unsigned blocks = (unsigned)(a.rblk_u * a.splits_u + a.rblk_p * a.splits_p);
+    constexpr int SM = TTAMM_INBATCH_SOFTMAX;
+    const int dp = (a.D + 31) / 32 * 32;
+    // the plan's rows per block: 256 with TTAMM_IB_WAVES=8, unless TTAMM_IB_KERNEL=p planned 128
+    if (!inbatch_pipelined() && inbatch_waves() == 8) {
+        switch (dp) {
+            case 32: hipLaunchKernelGGL((inbatch_x_kernel<32, 1, 8, true, SM>), dim3(blocks), dim3(512), 0, s, a); break;
+            case 64: hipLaunchKernelGGL((inbatch_x_kernel<64, 1, 8, true, SM>), dim3(blocks), dim3(512), 0, s, a); break;
+            case 96: hipLaunchKernelGGL((inbatch_x_kernel<96, 1, 8, true, SM>), dim3(blocks), dim3(512), 0, s, a); break;
+            default: hipLaunchKernelGGL((inbatch_x_kernel<128, 1, 8, true, SM>), dim3(blocks), dim3(512), 0, s, a); break;
+        }
+    } else {
+        switch (dp) {
+            case 32: hipLaunchKernelGGL((inbatch_x_kernel<32, 2, 4, false, SM>), dim3(blocks), dim3(256), 0, s, a); break;
+            case 64: hipLaunchKernelGGL((inbatch_x_kernel<64, 2, 4, false, SM>), dim3(blocks), dim3(256), 0, s, a); break;
+            case 96: hipLaunchKernelGGL((inbatch_x_kernel<96, 2, 4, false, SM>), dim3(blocks), dim3(256), 0, s, a); break;
+            default: hipLaunchKernelGGL((inbatch_x_kernel<128, 2, 4, false, SM>), dim3(blocks), dim3(256), 0, s, a); break;
+        }
+    }
+    TTAMM_LAUNCH_CHECK();
+    return launch_inbatch_reduce(a, s);
+}
+
+size_t inbatch_softmax_workspace_bytes(int64_t B, int64_t Bc, int D) {
+    return sizeof(float) * inbatch_lse_floats(B, Bc) + inbatch_standalone_workspace_bytes(B, Bc, D);
+}
+
+size_t inbatch_softmax_loss_workspace_bytes(int64_t B, int64_t Bc, int D) {
+    (void)D;
+    return sizeof(float) * inbatch_lse_floats(B, Bc);
+}
+
+int inbatch_softmax_loss_standalone(const float* U, int64_t B, int64_t ldu, const float* P, int64_t Bc, int64_t ldp,
+                                    int D, int64_t row_base, float inv_temperature, double* loss_sum, void* ws,
+                                    size_t ws_bytes, hipStream_t s) {
+    int rc;
+    TTAMM_REQUIRE(U && P && loss_sum && ws, "inbatch_softmax_loss: null argument");
+    TTAMM_REQUIRE(B > 0 && Bc > 0 && D > 0 && ldu >= D && ldp >= D, "inbatch_softmax_loss: bad shape");
+    TTAMM_REQUIRE(row_base >= 0 && row_base + B <= Bc,
+                  "inbatch_softmax_loss: row_base must place the B users' labels inside the Bc columns (0 <= row_base, "
+                  "row_base + B <= Bc)");
+    if ((rc = inbatch_softmax_check(inv_temperature))) return rc;
+    if ((rc = inbatch_loss_check(D))) return rc;
+    TTAMM_REQUIRE(ws_bytes >= inbatch_softmax_loss_workspace_bytes(B, Bc, D), "inbatch_softmax_loss: workspace too small");
+    InBatchLossArgs l{};
+    l.U = U, l.ldu = ldu, l.B = B, l.P = P, l.ldp = ldp, l.Bc = Bc, l.D = D;
+    l.row_base = row_base;
+    inbatch_lse_bind(l, static_cast<float*>(ws));
+    if ((rc = launch_inbatch_lse(l, inv_temperature, s))) return rc;
+    hipLaunchKernelGGL(ib_loss_sum_kernel, dim3(1), dim3(256), 0, s, l.loss_part, inbatch_lse_parts(B), loss_sum);
+    TTAMM_LAUNCH_CHECK();
+    return TTAMM_OK;
+}
+
+int inbatch_softmax_standalone(const float* U, int64_t B, int64_t ldu, const float* P, int64_t Bc, int64_t ldp, int D,
+                               int64_t row_base, float inv_count, float inv_temperature, float* dU, int64_t ld_du,
+                               float* dP, int64_t ld_dp, double* loss_sum, void* ws, size_t ws_bytes, hipStream_t s) {
+    int rc;
+    TTAMM_REQUIRE(U && P && dU && dP && loss_sum && ws, "inbatch_softmax: null argument");
+    TTAMM_REQUIRE(B > 0 && Bc > 0 && D > 0 && ldu >= D && ldp >= D && ld_du >= D && ld_dp >= D,
+                  "inbatch_softmax: bad shape");
+    TTAMM_REQUIRE(row_base >= 0 && row_base + B <= Bc,
+                  "inbatch_softmax: row_base must place the B users' labels inside the Bc columns (0 <= row_base, "
+                  "row_base + B <= Bc)");
+    if ((rc = inbatch_softmax_check(inv_temperature))) return rc;
+    if ((rc = inbatch_loss_check(D))) return rc;
+    TTAMM_REQUIRE(ws_bytes >= inbatch_softmax_workspace_bytes(B, Bc, D), "inbatch_softmax: workspace too small");
+    InBatchLossArgs l{};
+    l.U = U, l.ldu = ldu, l.B = B, l.P = P, l.ldp = ldp, l.Bc = Bc, l.D = D;
+    l.row_base = row_base;
+    float* w = static_cast<float*>(ws);
+    inbatch_lse_bind(l, w);
+    w += inbatch_lse_floats(B, Bc);
+    InBatchArgs a{};
+    a.U = U, a.ldu = ldu, a.B = B, a.P = P, a.ldp = ldp, a.Bc = Bc, a.D = D;
+    a.row_base = row_base, a.inv_T = inv_count;
+    size_t su, sp, parts;
+    inbatch_workspace_floats(B, Bc, D, &su, &sp, &parts);
+    a.slab_u = w, a.slab_p = w + su, a.loss_part = w + su + sp;
+    a.dU = dU, a.ld_du = ld_du, a.dP = dP, a.ld_dp = ld_dp;
+    if ((rc = launch_inbatch_softmax(a, l, inv_temperature, s))) return rc;
+    hipLaunchKernelGGL(ib_loss_sum_kernel, dim3(1), dim3(256), 0, s, l.loss_part, inbatch_lse_parts(B), loss_sum);
+    TTAMM_LAUNCH_CHECK();
+    return TTAMM_OK;
 }
 
 int inbatch_loss_standalone(const float* U, int64_t B, int64_t ldu, const float* P, int64_t Bc, int64_t ldp, int D,

@@ -396,6 +396,10 @@ struct InBatchArgs {
     // filled by inbatch_plan
     int rblk_u, rblk_p, splits_u, splits_p;
     int64_t cols_u, cols_p;
+    // softmax (launch_inbatch_softmax): inv_T is then inv_count / temperature
+    const float* rmax;   // [B] the rows' maximum of S * z_scale (the LSE pass's InBatchLossArgs.rmax)
+    const float* rinv;   // [B] 1 / the rows' sum of exp2(S * z_scale - rmax) (InBatchLossArgs.rinv)
+    float z_scale;       // log2(e) / temperature
 };
 void inbatch_plan(int64_t B, int64_t Bc, InBatchArgs& a);
 size_t inbatch_workspace_floats(int64_t B, int64_t Bc, int D, size_t* slab_u, size_t* slab_p, size_t* parts);
@@ -417,6 +421,14 @@ struct InBatchLossArgs {
     // filled by inbatch_loss_plan
     int rblk, splits;
     int64_t cols;
+    // softmax LSE pass (launch_inbatch_lse; loss_part is then the merge kernel's [inbatch_lse_parts(B)])
+    float z_scale;       // log2(e) / temperature
+    float* ms;           // [splits, B, 2] a split's (max, rescaled sum) of a row, log2 units
+    float* zpos;         // [B] the row's own positive's logit in log2 units
+    float* lse;          // [B] log2 of the row's sum of exp(S / temperature)
+    float* term;         // [B] the rows' loss terms, lse_b - S_bb / temperature
+    float* rmax;         // [B] the row's maximum logit in log2 units and
+    float* rinv;         // [B] 1 / its sum of exp2(z - rmax): the gradient pass's normaliser
 };
 void inbatch_loss_plan(int64_t B, int64_t Bc, InBatchLossArgs& a);
 int inbatch_loss_blocks(int64_t B, int64_t Bc);  // floats of loss_part
@@ -425,6 +437,26 @@ int launch_inbatch_loss(InBatchLossArgs& a, hipStream_t s);
 size_t inbatch_loss_workspace_bytes(int64_t B, int64_t Bc, int D);
 int inbatch_loss_standalone(const float* U, int64_t B, int64_t ldu, const float* P, int64_t Bc, int64_t ldp, int D,
                             int64_t row_base, double* loss_sum, void* ws, size_t ws_bytes, hipStream_t s);
+// In-batch softmax cross-entropy over the rows of S / temperature (ttamm.h ttamm_inbatch_softmax).
+// Two passes: the LSE pass (inbatch_loss_kernel's softmax form, then ib_lse_merge_kernel) owns the
+// loss and the rows' normalisers; the gradient pass is inbatch_x_kernel's softmax instantiation, which
+// reads (rmax, rinv) and accumulates no loss.  Always the split-bf16 inbatch_x_kernel: TTAMM_FP32_MFMA=exact and
+// TTAMM_IB_KERNEL=p are not honoured under softmax (neither variant has a softmax form).
+int inbatch_lse_parts(int64_t B);                     // floats of the merge kernel's loss_part
+size_t inbatch_lse_floats(int64_t B, int64_t Bc);     // ms + zpos + lse + term + rmax + rinv + loss_part
+void inbatch_lse_bind(InBatchLossArgs& a, float* w);  // a.B / a.Bc set; w holds inbatch_lse_floats
+int inbatch_softmax_check(float inv_temperature);     // finite and > 0
+int launch_inbatch_lse(InBatchLossArgs& a, float inv_temperature, hipStream_t s);
+// a.rmax / a.rinv / a.z_scale are taken from the LSE pass l, which is launched first; a.inv_T = inv_count
+int launch_inbatch_softmax(InBatchArgs& a, InBatchLossArgs& l, float inv_temperature, hipStream_t s);
+size_t inbatch_softmax_workspace_bytes(int64_t B, int64_t Bc, int D);
+int inbatch_softmax_standalone(const float* U, int64_t B, int64_t ldu, const float* P, int64_t Bc, int64_t ldp, int D,
+                               int64_t row_base, float inv_count, float inv_temperature, float* dU, int64_t ld_du,
+                               float* dP, int64_t ld_dp, double* loss_sum, void* ws, size_t ws_bytes, hipStream_t s);
+size_t inbatch_softmax_loss_workspace_bytes(int64_t B, int64_t Bc, int D);
+int inbatch_softmax_loss_standalone(const float* U, int64_t B, int64_t ldu, const float* P, int64_t Bc, int64_t ldp,
+                                    int D, int64_t row_base, float inv_temperature, double* loss_sum, void* ws,
+                                    size_t ws_bytes, hipStream_t s);
 
 // ------------------------------------------------------------------------------------
 // Exact inner-product retrieval + top-k (retrieval.hip)

@@ -42,6 +42,9 @@ struct StepWs {
     float* ib_du = nullptr;   // [B, D]
     float* ib_dp = nullptr;   // [B, D] (one process; sharded: the caller's inbatch_dp)
     int ib_parts = 0;
+    // softmax objective (ttamm_step_args.in_batch_loss): the LSE pass, which owns the loss
+    bool ib_softmax = false;
+    InBatchLossArgs ib_lse{};
     bool cal_on = false;  // category-alignment loss this step
     CalArgs cal{};
     // gradient clipping (ttamm_hparams.grad_clip_norm)
@@ -61,6 +64,8 @@ bool sharded(const ttamm_step_args& A) { return A.phase != TTAMM_PHASE_ALL; }
 // compact exchange rows (ttamm.h ttamm_step_args.exchange_counts)
 bool compact_exchange(const ttamm_step_args& A) { return sharded(A) && A.exchange_counts != nullptr; }
 int64_t global_batch(const ttamm_step_args& A) { return A.global_batch > 0 ? A.global_batch : A.b.batch; }
+// the in-batch objective is the softmax cross-entropy over the rows of S (ttamm.h in_batch_loss)
+bool softmax_loss(const ttamm_step_args& A) { return A.in_batch_loss == TTAMM_INBATCH_SOFTMAX; }
 
 // Workspace layout.  Deterministic in the arguments, so every phase call of a sharded step
 // finds the previous phases' activations where it left them.
@@ -160,6 +165,12 @@ int plan(Arena& ar, const ttamm_step_args& A, StepWs& ws) {
         ws.ib_parts = (int)parts;
         ws.ib_du = ar.take<float>((size_t)B * D);
         if (!shard) ws.ib_dp = ar.take<float>((size_t)B * D);
+        if (softmax_loss(A)) {
+            ws.ib_softmax = true;
+            ws.ib_lse.B = B, ws.ib_lse.Bc = Bc;
+            float* w = ar.take<float>(inbatch_lse_floats(B, Bc));
+            if (!ar.measuring) inbatch_lse_bind(ws.ib_lse, w);
+        }
     }
     if (cal_enabled(A)) {
         // one process: the batch's item rows; sharded: this requester's rows, with the per-category
@@ -821,7 +832,10 @@ CalArgs& bind_cal_grads(Step& st) {
 
 // in-batch negatives: the positives every user is scored against; the BCE terms of the step
 int64_t inbatch_cols(const Step& st) { return st.ws.ib_on ? (sharded(st.A) ? st.Bg : st.B) : 0; }
-int64_t bce_count(const Step& st) { return st.Bg * ((st.ws.ib_on ? inbatch_cols(st) : 1) + st.N); }
+// (softmax: the mean is over the B rows' terms)
+int64_t bce_count(const Step& st) {
+    return st.ws.ib_softmax ? st.B : st.Bg * ((st.ws.ib_on ? inbatch_cols(st) : 1) + st.N);
+}
 
 // S = U P^T, its BCE, dU and dP: one process against the batch's own positives, sharded against
 // every rank's (inbatch_items)
@@ -840,7 +854,7 @@ InBatchArgs& bind_inbatch(Step& st) {
     a.Bc = inbatch_cols(st);
     a.D = D;
     a.row_base = shard ? A.row_base : 0;
-    a.inv_T = 1.0f / (float)(st.Bg * (inbatch_cols(st) + st.N));
+    a.inv_T = 1.0f / (float)bce_count(st);
     a.dU = st.ws.ib_du;
     a.ld_du = D;
     return a;
@@ -849,7 +863,14 @@ int run_inbatch(Step& st, hipStream_t s) {
     int rc;
     void* const* ev = st.A.timing_events + 4;
     if (ev[0] && ev[1]) TTAMM_HIP(hipEventRecord((hipEvent_t)ev[0], s));
-    if ((rc = launch_inbatch(bind_inbatch(st), s))) return rc;
+    InBatchArgs& a = bind_inbatch(st);
+    if (st.ws.ib_softmax) {  // the LSE pass (the rows' normalisers, the loss partials), then the softmax gradient kernel
+        InBatchLossArgs& l = st.ws.ib_lse;
+        l.U = a.U, l.ldu = a.ldu, l.P = a.P, l.ldp = a.ldp, l.D = a.D, l.row_base = a.row_base;
+        if ((rc = launch_inbatch_softmax(a, l, st.A.in_batch_inv_temperature, s))) return rc;
+    } else if ((rc = launch_inbatch(a, s))) {
+        return rc;
+    }
     if (ev[0] && ev[1]) TTAMM_HIP(hipEventRecord((hipEvent_t)ev[1], s));
     return TTAMM_OK;
 }
@@ -914,8 +935,10 @@ int loss_finalize(const Step& st, hipStream_t s) {
     const ttamm_step_args& A = st.A;
     const StepWs& ws = st.ws;
     if (!A.loss_out) return TTAMM_OK;
-    return launch_loss_finalize(ws.partials, ws.score_blocks, ws.ib_on ? ws.ib.loss_part : nullptr,
-                                ws.ib_on ? ws.ib_parts : 0, bce_count(st), st.B, st.Bg, st.D,
+    // softmax: the LSE pass's block partials (the scorer adds no retrieval term with N = 0)
+    const float* ib_part = ws.ib_softmax ? ws.ib_lse.loss_part : ws.ib_on ? ws.ib.loss_part : nullptr;
+    const int ib_parts = ws.ib_softmax ? inbatch_lse_parts(st.B) : ws.ib_on ? ws.ib_parts : 0;
+    return launch_loss_finalize(ws.partials, ws.score_blocks, ib_part, ib_parts, bce_count(st), st.B, st.Bg, st.D,
                                 (float)A.hp.lambda_mimic_user, (float)A.hp.lambda_mimic_item, st.mimic ? 1 : 0,
                                 ws.cal_on && A.row_base == 0 ? ws.cal.out : nullptr,
                                 (float)A.hp.lambda_category_alignment, A.loss_out, A.loss_accum, A.status, s);
@@ -943,6 +966,18 @@ int validate_step(const ttamm_step_args& A) {
         TTAMM_REQUIRE(A.major_category >= 0 && A.major_category < A.num_categories,
                       "category alignment: major_category out of range");
         TTAMM_REQUIRE(D <= 256, "category alignment: embedding dim must be <= 256");
+    }
+    TTAMM_REQUIRE(A.in_batch_loss == TTAMM_INBATCH_BCE || A.in_batch_loss == TTAMM_INBATCH_SOFTMAX,
+                  "in_batch_loss must be 0 (the BCE mean) or 1 (the softmax cross-entropy)");
+    if (A.in_batch_loss != TTAMM_INBATCH_BCE) {
+        TTAMM_REQUIRE(!sharded(A),
+                      "in_batch_loss: the softmax objective needs phase == 0, the whole step in one call (it is not "
+                      "built for the row-sharded step)");
+        TTAMM_REQUIRE(A.in_batch != 0, "in_batch_loss: the softmax objective needs in_batch");
+        TTAMM_REQUIRE(A.b.num_neg == 0,
+                      "in_batch_loss: the softmax objective needs b.num_neg == 0 (sampled negatives do not join the "
+                      "denominator)");
+        if ((rc = inbatch_softmax_check(A.in_batch_inv_temperature))) return rc;
     }
     if (A.in_batch) {
         TTAMM_REQUIRE(A.b.num_neg >= 0, "num_negatives must be >= 0 with in-batch negatives");

@@ -14,7 +14,7 @@ from .encoders import (
     build_id_embedding,
     build_tower_encoder,
 )
-from .inbatch import inbatch_bce, inbatch_bce_loss
+from .inbatch import inbatch_bce, inbatch_bce_loss, inbatch_softmax, inbatch_softmax_loss
 from .metrics import RankingMetrics, compute_ranking_metrics, evaluate_metrics, ranking_metrics
 from .retrieval import encode_item_embeddings, evaluate_model, prepare_faiss_resources, topk_merge
 from .samplers import PositivesCSR, sample_negative_items
@@ -51,6 +51,8 @@ __all__ = [
     "evaluate_model",
     "inbatch_bce",
     "inbatch_bce_loss",
+    "inbatch_softmax",
+    "inbatch_softmax_loss",
     "load_features",
     "load_interactions",
     "prepare_faiss_resources",

@@ -182,6 +182,9 @@ class StepArgs(ctypes.Structure):
         ("exchange_counts", c_vp),
         ("exchange_counts_ld", c_i64),
         ("exchange_world", c_i32),
+        # the in-batch objective (ttamm.h TTAMM_INBATCH_*)
+        ("in_batch_loss", c_i32),
+        ("in_batch_inv_temperature", c_f),
     ]
 
 
@@ -190,6 +193,8 @@ G0_EXACT = 0  # ttamm.h TTAMM_G0_EXACT
 DENSE_ADAM = 0  # ttamm.h TTAMM_DENSE_ADAM
 DENSE_SGD = 1  # ttamm.h TTAMM_DENSE_SGD
 G0_FAST = 1  # ttamm.h TTAMM_G0_FAST
+INBATCH_BCE = 0  # ttamm.h TTAMM_INBATCH_BCE
+INBATCH_SOFTMAX = 1  # ttamm.h TTAMM_INBATCH_SOFTMAX
 
 # ttamm.h TTAMM_PHASE_*
 PHASE_ALL = 0
@@ -304,6 +309,17 @@ SIGNATURES = {
     "ttamm_inbatch_bce_loss": (
         ctypes.c_int,
         [c_vp, c_i64, c_i64, c_vp, c_i64, c_i64, c_i32, c_i64, c_vp, c_vp, ctypes.c_size_t, c_vp],
+    ),
+    "ttamm_inbatch_softmax_workspace_size": (ctypes.c_size_t, [c_i64, c_i64, c_i32]),
+    "ttamm_inbatch_softmax": (
+        ctypes.c_int,
+        [c_vp, c_i64, c_i64, c_vp, c_i64, c_i64, c_i32, c_i64, ctypes.c_float, ctypes.c_float, c_vp, c_i64, c_vp, c_i64,
+         c_vp, c_vp, ctypes.c_size_t, c_vp],
+    ),
+    "ttamm_inbatch_softmax_loss_workspace_size": (ctypes.c_size_t, [c_i64, c_i64, c_i32]),
+    "ttamm_inbatch_softmax_loss": (
+        ctypes.c_int,
+        [c_vp, c_i64, c_i64, c_vp, c_i64, c_i64, c_i32, c_i64, ctypes.c_float, c_vp, c_vp, ctypes.c_size_t, c_vp],
     ),
 }
 

@@ -473,6 +473,8 @@ class ShardedTrainStep(FusedTrainStep):
 
     def __init__(self, model, optimizers, *, world_size: int, rank: int, num_items: int,
                  comm: Callable[[Program], Any] | None = None, group_towers: bool = True, **kw: Any) -> None:
+        if kw.get("in_batch_loss", "bce") == "softmax":  # before any collective or device use
+            raise NotImplementedError("in_batch_loss='softmax' is not built for the row-sharded step")
         clip = kw.get("gradient_clip_norm")
         if clip is not None and clip > 0 and not group_towers:
             raise NotImplementedError("ttamm: gradient clipping in the row-sharded step needs group_towers=True")

@@ -18,6 +18,7 @@ their format.
 from __future__ import annotations
 
 import ctypes
+import math
 from typing import Any, Callable, Iterable, Mapping, Sequence
 
 import torch
@@ -120,8 +121,32 @@ def _dense_params(opt: torch.optim.Optimizer) -> list[torch.Tensor]:
     return [p for g in opt.param_groups for p in g["params"]]
 
 
+def _in_batch_objective(in_batch_loss: str, temperature: float, in_batch: bool, num_neg: int) -> tuple[int, float]:
+    """The in-batch objective's keywords -> (ttamm.h TTAMM_INBATCH_*, 1 / temperature).  "softmax"
+    (the cross-entropy over each user's row of the in-batch logits / temperature) needs in-batch
+    mode and no sampled negatives.  Raises before any device use."""
+    if in_batch_loss not in ("bce", "softmax"):
+        raise ValueError(f"in_batch_loss must be 'bce' or 'softmax', got {in_batch_loss!r}")
+    t = float(temperature)
+    if not math.isfinite(t) or t <= 0.0:
+        raise ValueError("temperature must be finite and greater than zero")
+    if in_batch_loss == "bce":
+        return _lib.INBATCH_BCE, 1.0 / t
+    if not in_batch:
+        raise ValueError("in_batch_loss='softmax' needs in_batch_negatives=True")
+    if num_neg != 0:
+        raise ValueError("in_batch_loss='softmax' needs negatives_per_positive == 0 (sampled negatives do not join "
+                         "the softmax denominator)")
+    return _lib.INBATCH_SOFTMAX, 1.0 / t
+
+
 class FusedTrainStep:
-    """Owns the native step descriptor and workspace for one (model, optimizers) pair."""
+    """Owns the native step descriptor and workspace for one (model, optimizers) pair.
+
+    ``in_batch_loss="softmax"`` (with ``in_batch_negatives=True`` and ``negatives_per_positive == 0``)
+    trains on the softmax cross-entropy over each user's row of the in-batch logits divided by
+    ``temperature`` instead of the BCE mean; ``last_losses()["bce"]`` (``loss_out[1]``) then carries
+    the softmax mean."""
 
     def __init__(
         self,
@@ -146,7 +171,11 @@ class FusedTrainStep:
         in_batch_negatives: bool = False,
         gradient_clip_norm: float | None = None,
         feature_planes: bool = False,
+        in_batch_loss: str = "bce",
+        temperature: float = 1.0,
     ) -> None:
+        self.in_batch_loss, self.inv_temperature = _in_batch_objective(
+            in_batch_loss, temperature, bool(in_batch_negatives), int(negatives_per_positive))
         # feature_planes (developer option, off by default): fp32 towers keep their feature rows
         # pre-split into bf16 hi / mid / lo planes (1.5x the fp32 rows' bytes in HBM) for the first
         # layer's forward and weight gradient instead of splitting them inside the GEMMs (same
@@ -293,6 +322,8 @@ class FusedTrainStep:
             setattr(args, name, desc)
         args.mimic_enabled = 1 if mimic is not None else 0
         args.in_batch = 1 if self.in_batch else 0
+        args.in_batch_loss = self.in_batch_loss
+        args.in_batch_inv_temperature = self.inv_temperature
         lw = dict(loss_weights or {})
         args.hp.lambda_mimic_user = float(lw.get("mimic_user", 0.0))
         args.hp.lambda_mimic_item = float(lw.get("mimic_item", 0.0))
@@ -617,6 +648,8 @@ class FusedTrainStep:
         return total / max(count, 1.0)
 
     def last_losses(self) -> dict[str, float]:
+        """The last step's losses.  "bce" is the retrieval term: the BCE mean, or under
+        ``in_batch_loss="softmax"`` the softmax cross-entropy mean."""
         v = self.loss_out.tolist()
         return {"total": v[0], "bce": v[1], "mimic_user": v[2], "mimic_item": v[3], "category_alignment": v[4]}
 
@@ -656,6 +689,8 @@ def train_one_epoch(
     step_losses: list | None = None,
     in_batch_negatives: bool = False,
     table_adamw_math: str = "exact",
+    in_batch_loss: str = "bce",
+    temperature: float = 1.0,
 ) -> float:
     """Drop-in for ``_train_one_epoch`` (training.py:700-833) executed on the MI355X.
 
@@ -669,7 +704,11 @@ def train_one_epoch(
     ``in_batch_negatives`` selects ttamm's in-batch mode (FusedTrainStep; BASELINE C2/C4), with
     ``negatives_per_positive`` sampled negatives on top (0 allowed).  ``table_adamw_math``: the
     g = 0 AdamW arithmetic of untouched mimic-table rows — "exact" (default, bit-identical to
-    torch) or "fast" (v_sqrt / v_rcp, within a few ulp of torch per step; FusedTrainStep)."""
+    torch) or "fast" (v_sqrt / v_rcp, within a few ulp of torch per step; FusedTrainStep).
+    ``in_batch_loss="softmax"`` with ``temperature`` trains on the in-batch softmax cross-entropy
+    (needs ``in_batch_negatives=True`` and ``negatives_per_positive == 0``); ``step_losses`` then
+    carry its mean in the ``bce`` slot."""
+    _in_batch_objective(in_batch_loss, temperature, bool(in_batch_negatives), int(negatives_per_positive))
     model.train()
     if not isinstance(criterion, nn.BCEWithLogitsLoss) or criterion.reduction != "mean" or \
             criterion.weight is not None or criterion.pos_weight is not None:
@@ -692,7 +731,7 @@ def train_one_epoch(
                 max_batch=max(int(size), users.numel()),
                 item_category_tensor=item_category_tensor, major_category_id=major_category_id,
                 in_batch_negatives=in_batch_negatives, gradient_clip_norm=gradient_clip_norm,
-                table_adamw_math=table_adamw_math,
+                table_adamw_math=table_adamw_math, in_batch_loss=in_batch_loss, temperature=temperature,
             )
         neg = masks = None
         if batch_hook is not None:
@@ -723,7 +762,10 @@ class FusedEvalLoss:
     ``in_batch_negatives=True`` (ttamm's in-batch mode, not reference behaviour) makes every batch
     one ``ttamm_eval_loss_inbatch`` call: the BCE mean over the [B, B] logits users x positives
     (label 1 on the diagonal, never stored) and the ``negatives_per_positive >= 0`` sampled
-    negatives, the objective ``FusedTrainStep(in_batch_negatives=True)`` trains on."""
+    negatives, the objective ``FusedTrainStep(in_batch_negatives=True)`` trains on.
+    ``in_batch_loss="softmax"`` with ``temperature`` makes it the softmax cross-entropy mean over the
+    rows of the [B, B] logits instead (``negatives_per_positive == 0``; one log-sum-exp pass per
+    batch), reported in the same slots."""
 
     def __init__(
         self,
@@ -737,8 +779,12 @@ class FusedEvalLoss:
         seed: int | None = None,
         num_items: int | None = None,
         in_batch_negatives: bool = False,
+        in_batch_loss: str = "bce",
+        temperature: float = 1.0,
     ) -> None:
         self.in_batch = bool(in_batch_negatives)
+        self.in_batch_loss, self.inv_temperature = _in_batch_objective(
+            in_batch_loss, temperature, self.in_batch, int(negatives_per_positive))
         if negatives_per_positive < 0 or (negatives_per_positive == 0 and not self.in_batch):
             raise ValueError("num_negatives must be greater than zero.")
         self.model = model
@@ -775,6 +821,8 @@ class FusedEvalLoss:
                 desc.feat_bf16_ld = f16.stride(0)
             setattr(args, name, desc)
         args.mimic_enabled = 1 if mimic is not None else 0
+        args.in_batch_loss = self.in_batch_loss
+        args.in_batch_inv_temperature = self.inv_temperature
         args.b.num_neg = self.num_neg
         self.csr = None
         if positives is not None and self.num_neg > 0:  # in-batch with N == 0 draws nothing
@@ -895,6 +943,8 @@ def compute_loss(
     batch_hook: Callable[[int, torch.Tensor, torch.Tensor], Any] | None = None,
     seed: int | None = None,
     in_batch_negatives: bool = False,
+    in_batch_loss: str = "bce",
+    temperature: float = 1.0,
 ) -> float:
     """Drop-in for ``_compute_loss`` (training.py:836-914) executed on the MI355X: the model is put
     (and left) in eval mode, every batch is one ``ttamm_eval_loss`` call with no host
@@ -910,7 +960,9 @@ def compute_loss(
     every batch is one ``ttamm_eval_loss_inbatch`` call, the BCE mean over the [B, B] in-batch
     logits and the ``negatives_per_positive >= 0`` sampled negatives.  With
     ``negatives_per_positive == 0`` a hook's negatives are ignored and ``user_positive_items`` may
-    be empty or None."""
+    be empty or None.  ``in_batch_loss="softmax"`` with ``temperature`` validates on the in-batch
+    softmax cross-entropy instead (``negatives_per_positive == 0``)."""
+    _in_batch_objective(in_batch_loss, temperature, bool(in_batch_negatives), int(negatives_per_positive))
     model.eval()
     if not isinstance(criterion, nn.BCEWithLogitsLoss) or criterion.reduction != "mean" or \
             criterion.weight is not None or criterion.pos_weight is not None:
@@ -929,6 +981,7 @@ def compute_loss(
                 model, negatives_per_positive=negatives_per_positive, positives=user_positive_items,
                 user_features=user_features, item_features=item_features,
                 max_batch=max(int(size), users.numel()), seed=seed, in_batch_negatives=in_batch_negatives,
+                in_batch_loss=in_batch_loss, temperature=temperature,
             )
         neg = None
         if batch_hook is not None:
