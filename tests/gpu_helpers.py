@@ -36,7 +36,8 @@ def ttamm_optimizers(model, *, lr=1e-3, betas=(0.9, 0.999), weight_decay=0.01, o
 
 
 def run_ttamm(prob: Problem, *, lr=1e-3, betas=(0.9, 0.999), weight_decay=0.01, steps=None, device="cuda",
-              gradient_clip_norm=None, optimizer="adamw", momentum=0.0, deferred_adamw=True):
+              gradient_clip_norm=None, optimizer="adamw", momentum=0.0, deferred_adamw=True, **engine_kwargs):
+    """``engine_kwargs`` go to ttamm.FusedTrainStep as given (feature_planes=, seed=, ...)."""
     model = ttamm_model_from(prob, device)
     opts = ttamm_optimizers(model, lr=lr, betas=betas, weight_decay=weight_decay, optimizer=optimizer,
                             momentum=momentum)
@@ -44,7 +45,7 @@ def run_ttamm(prob: Problem, *, lr=1e-3, betas=(0.9, 0.999), weight_decay=0.01, 
         model, opts, negatives_per_positive=prob.shape.N, positives=prob.positives,
         user_features=prob.user_features.to(device), item_features=prob.item_features.to(device),
         loss_weights=LOSS_WEIGHTS, max_batch=prob.shape.B, gradient_clip_norm=gradient_clip_norm,
-        deferred_adamw=deferred_adamw,
+        deferred_adamw=deferred_adamw, **engine_kwargs,
     )
     losses = []
     for (users, pos, neg, um, im) in prob.batches[: steps or len(prob.batches)]:

@@ -902,10 +902,12 @@ __global__ __launch_bounds__(kThreads, CX::MINB) void gemm_x_kernel(GemmBatch ba
             for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
     // weight gradients with b_colsum: the blocks of M-tile 0 sum the dY values they stage (the
     // bias gradient, written to C row M after the main loop)
-    // (bf16 towers and pre-split X planes only: the fp32 split kernels take the bias gradient as an
-    // implicit ones column of X — the column-sum registers pushed the 128 x 192 fp32 weight gradient
-    // to 256 VGPRs with scratch spills, C2 +6 us per step, profiles/r06_s2_bisect.txt)
-    constexpr bool CSUM = AK && BKM && (PL == 1 || CX::APL);
+    // (bf16 towers only: the fp32 split kernels, pre-split X planes included, take the bias gradient
+    // as an implicit ones column of X — the column-sum registers pushed the 128 x 192 fp32 weight
+    // gradient to 256 VGPRs with scratch spills, C2 +6 us per step, profiles/r06_s2_bisect.txt; and
+    // a column sum adds dY in another order than the MFMAs do, so the plane kernels' bias gradient
+    // differed from the default path's in its last bits)
+    constexpr bool CSUM = AK && BKM && PL == 1;
     const bool colsum = CSUM && P.b_colsum && tm == 0;
     float4 bsum[CSUM ? CX::B_LOADS : 1];
 #pragma unroll
@@ -997,7 +999,26 @@ __global__ __launch_bounds__(kThreads, CX::MINB) void gemm_x_kernel(GemmBatch ba
                     // a value select per component (a select of the two float4 objects compiled to a
                     // select of their addresses: both spilled to scratch)
                     const float4 r = ra[RA][it];
-                    const float4 v = make_float4(ok ? r.x : 0.f, ok ? r.y : 0.f, ok ? r.z : 0.f, ok ? r.w : 0.f);
+                    float4 v = make_float4(ok ? r.x : 0.f, ok ? r.y : 0.f, ok ? r.z : 0.f, ok ? r.w : 0.f);
+                    if constexpr (AK && !FAST) {
+                        // the implicit all-ones column of X (P.a_ones_col; a tile that holds it is never
+                        // FAST): bf16 1.0 in the hi plane of every k row of the split, zero in mid and lo
+                        // — the planes split_bf16 forms of 1.0f, so the bias gradient takes the same
+                        // MFMA sums as in the kernel that splits X itself
+                        const int c48 = (tid + it * kThreads) % 48, ph = c48 % 6;
+                        const int one = P.a_ones_col - m0 - ((c48 / 6) * 16 + (ph & 1) * 8);  // element of this piece
+                        if (P.a_ones_col >= 0 && (ph >> 1) == 0 && one >= 0 && one < 8 && k0 + a_r[it] < k_end) {
+                            uint32_t w4[4] = {__float_as_uint(v.x), __float_as_uint(v.y), __float_as_uint(v.z),
+                                              __float_as_uint(v.w)};
+#pragma unroll
+                            for (int c = 0; c < 4; ++c) {
+                                if (one == 2 * c) w4[c] = (w4[c] & 0xFFFF0000u) | 0x3F80u;
+                                if (one == 2 * c + 1) w4[c] = (w4[c] & 0x0000FFFFu) | 0x3F800000u;
+                            }
+                            v = make_float4(__uint_as_float(w4[0]), __uint_as_float(w4[1]), __uint_as_float(w4[2]),
+                                            __uint_as_float(w4[3]));
+                        }
+                    }
                     *reinterpret_cast<float4*>(Ap2 + ap_lds[it]) = v;
                     return;
                 }
@@ -1963,9 +1984,9 @@ int launch_wgrad(WgradBatch& wb, hipStream_t s, void* const* ev) {
         p.B = w.dY;
         p.ldb = w.ld_dy;
         p.b_kn = 1;
-        // bf16 / pre-split-plane kernels: the bias gradient as column sums of dY in the M-tile-0
-        // blocks (b_colsum), so M = n_in; the fp32 split and fp32-MFMA kernels: the implicit ones
-        // column (M = n_in + 1)
+        // bf16 kernels: the bias gradient as column sums of dY in the M-tile-0 blocks (b_colsum), so
+        // M = n_in; the fp32 split (X pre-split into planes or not) and fp32-MFMA kernels: the
+        // implicit ones column (M = n_in + 1)
         p.b_colsum = 0;
         p.a_ones_col = w.N;
         p.M = w.N + 1;
@@ -1986,7 +2007,7 @@ int launch_wgrad(WgradBatch& wb, hipStream_t s, void* const* ev) {
             p.A3p = w.X3p;
             p.lda3 = w.ld_x3;
         }
-        if (!exact && (bf || planes)) {  // (the column-sum kernels: see gemm_x_kernel CSUM)
+        if (!exact && bf) {  // (the column-sum kernels: see gemm_x_kernel CSUM)
             p.b_colsum = 1;
             p.a_ones_col = -1;
             p.M = w.N;
