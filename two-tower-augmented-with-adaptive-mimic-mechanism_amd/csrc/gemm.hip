@@ -157,9 +157,10 @@ __device__ __forceinline__ float act_grad(int act, float z) {
     }
 }
 
+// hv_pre (EPI_DGRAD_HIDDEN): the aux0 group of (row, col) the caller already holds in registers
 template <int E>
 __device__ __forceinline__ void epilogue4(const KArg(GemmProblem) & P, float4 v, float4 bias4, int split, int row,
-                                          int col) {
+                                          int col, const float4* hv_pre = nullptr) {
     const int N = P.N;
     float x[4] = {v.x + bias4.x, v.y + bias4.y, v.z + bias4.z, v.w + bias4.w};
     static_assert(E != EPI_HIDDEN, "EPI_HIDDEN runs through epilogue8_hidden");
@@ -203,7 +204,7 @@ __device__ __forceinline__ void epilogue4(const KArg(GemmProblem) & P, float4 v,
             x[2] += dt.z * (1.0f - g.z), x[3] += dt.w * (1.0f - g.w);
         }
     } else if (E == EPI_DGRAD_HIDDEN) {
-        const float4 hv = ld4(P.aux0 + (int64_t)row * P.ld_aux0 + col);
+        const float4 hv = hv_pre ? *hv_pre : ld4(P.aux0 + (int64_t)row * P.ld_aux0 + col);
         if (P.act == TTAMM_ACT_RELU) {  // aux0 = the stored hidden output: > 0 iff ReLU passed and kept
             x[0] = hv.x > 0.f ? x[0] * P.inv_keep : 0.f, x[1] = hv.y > 0.f ? x[1] * P.inv_keep : 0.f;
             x[2] = hv.z > 0.f ? x[2] * P.inv_keep : 0.f, x[3] = hv.w > 0.f ? x[3] * P.inv_keep : 0.f;
@@ -742,6 +743,11 @@ typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
 #ifndef TTAMM_BF16_DEEP
 #define TTAMM_BF16_DEEP 1
 #endif
+// The dgrad epilogue's aux0 rows loaded a phase at a time ahead of the Cs barrier (gemm_x_kernel);
+// -DTTAMM_DGRAD_PREFETCH=0: the loads inside the row loop, for A/B runs
+#ifndef TTAMM_DGRAD_PREFETCH
+#define TTAMM_DGRAD_PREFETCH 1
+#endif
 // x -> (hi, mid, lo) bf16 quadruples, 8 bytes each
 template <int PL>
 __device__ __forceinline__ void split_bf16(float4 v, uint2 out[PL]) {
@@ -1242,9 +1248,33 @@ __global__ __launch_bounds__(kThreads, CX::MINB) void gemm_x_kernel(GemmBatch ba
 
     // ---- epilogue through LDS, in row slices (as gemm_kernel) ---------------------------------
     float* Cs = reinterpret_cast<float*>(lds);
+    // EPI_DGRAD_HIDDEN over a ReLU layer: the stored hidden rows (aux0, only their sign is used)
+    // come from HBM, and the k-loop they follow (K = 96: six k-tiles) is shorter than one round
+    // trip.  A thread's loads for a whole phase are issued together before the barrier that
+    // publishes Cs — and, where two sets fit the register budget (PRE2), the next phase's before
+    // this phase's row loop — instead of unroll-by-4 batches of dependent loads inside it.
+    constexpr int PC4 = BN / 4, PRSTEP = kThreads / PC4;
+    constexpr bool PRE = TTAMM_DGRAD_PREFETCH && E == EPI_DGRAD_HIDDEN;
+    constexpr int PRE_ROWS = PRE ? (CX::EPI_ROWS + PRSTEP - 1) / PRSTEP : 1;
+    constexpr bool PRE2 = PRE && PRE_ROWS <= 8 && CX::EPI_PHASES > 1;
+    float4 hv_cur[PRE_ROWS] = {}, hv_nxt[PRE_ROWS] = {};
+    const int pcol = n0 + (tid % PC4) * 4, pr0 = tid / PC4;
+    const bool pre = PRE && P.act == TTAMM_ACT_RELU && pr0 < PRSTEP && pcol < N;
+    auto prefetch = [&](int ph, float4(&hv)[PRE_ROWS]) {
+        const int row_lo = ph * CX::EPI_ROWS;
+        const int rows_here = min(CX::EPI_ROWS, BM - row_lo);
+        if (!pre) return;
+#pragma unroll
+        for (int k = 0; k < PRE_ROWS; ++k) {
+            const int rr = pr0 + k * PRSTEP, row = m0 + row_lo + rr;
+            if (rr < rows_here && row < M) hv[k] = ld4(P.aux0 + (int64_t)row * P.ld_aux0 + pcol);
+        }
+    };
+    if constexpr (PRE2) prefetch(0, hv_cur);
     for (int ph = 0; ph < CX::EPI_PHASES; ++ph) {
         const int row_lo = ph * CX::EPI_ROWS;
         const int rows_here = min(CX::EPI_ROWS, BM - row_lo);
+        if constexpr (PRE && !PRE2) prefetch(ph, hv_cur);
 #pragma unroll
         for (int i = 0; i < I; ++i) {
             const int br = wm * TM + i * 32;
@@ -1281,15 +1311,30 @@ __global__ __launch_bounds__(kThreads, CX::MINB) void gemm_x_kernel(GemmBatch ba
             constexpr int RSTEP = kThreads / C4;
             const int c4 = tid % C4, r0 = tid / C4;
             const int col = n0 + c4 * 4;
+            if constexpr (PRE2)
+                if (ph + 1 < CX::EPI_PHASES) prefetch(ph + 1, hv_nxt);
             if (r0 < RSTEP && col < N) {
                 const bool has_bias = (E == EPI_STORE || E == EPI_HIDDEN || E == EPI_GATE_HIDDEN || E == EPI_GATE_OUT) &&
                                       P.bias != nullptr;
                 const float4 bias4 = has_bias ? ld4(P.bias + col) : make_float4(0.f, 0.f, 0.f, 0.f);
+                if (PRE && pre) {  // the rows prefetch() loaded, under its conditions
+#pragma unroll
+                    for (int k = 0; k < PRE_ROWS; ++k) {
+                        const int rr = r0 + k * RSTEP, row = m0 + row_lo + rr;
+                        if (rr < rows_here && row < M)
+                            epilogue4<E>(P, ld4(Cs + rr * CX::CLD + c4 * 4), bias4, split, row, col, &hv_cur[k]);
+                    }
+                } else {
 #pragma unroll 4
-                for (int rr = r0; rr < rows_here; rr += RSTEP) {
-                    const int row = m0 + row_lo + rr;
-                    if (row < M) epilogue4<E>(P, ld4(Cs + rr * CX::CLD + c4 * 4), bias4, split, row, col);
+                    for (int rr = r0; rr < rows_here; rr += RSTEP) {
+                        const int row = m0 + row_lo + rr;
+                        if (row < M) epilogue4<E>(P, ld4(Cs + rr * CX::CLD + c4 * 4), bias4, split, row, col);
+                    }
                 }
+            }
+            if constexpr (PRE2) {
+#pragma unroll
+                for (int k = 0; k < PRE_ROWS; ++k) hv_cur[k] = hv_nxt[k];
             }
         }
         __syncthreads();
@@ -1512,6 +1557,7 @@ __global__ void to_planes_kernel(const float* __restrict__ src, int64_t rows, in
 }
 
 // grad_w[m_out][n_in] = sum_s slab[s][n_in][m_out] ; grad_b[m_out] = sum_s slab[s][N_in][m_out]
+constexpr int kWgradReduceDepth = 16;  // slab loads in flight per thread
 __global__ void wgrad_reduce_kernel(WgradBatch batch, int64_t total) {
     const KArg(WgradBatch)* kb = (const KArg(WgradBatch)*)(__builtin_amdgcn_kernarg_segment_ptr());
     const int64_t gid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -1527,18 +1573,31 @@ __global__ void wgrad_reduce_kernel(WgradBatch batch, int64_t total) {
     const int Mo = P.M;
     const int64_t plane = (int64_t)(P.N + 1) * Mo;
     const int n = (int)(off / Mo), m = (int)(off - (int64_t)n * Mo);
-    // fixed summation order (split 0, 1, ...); the loads of 8 splits are issued before their adds
+    // fixed summation order (split 0, 1, ...); the loads of kWgradReduceDepth splits are issued
+    // before their adds, the last partial chunk's too (loads past the end re-read the last split
+    // and are not added)
     float s = 0.f;
     const float* src = P.slab + off;
+    const int splits = P.splits;
     int sp = 0;
-    for (; sp + 8 <= P.splits; sp += 8) {
-        float v[8];
+    for (; sp + kWgradReduceDepth <= splits; sp += kWgradReduceDepth) {
+        float v[kWgradReduceDepth];
 #pragma unroll
-        for (int i = 0; i < 8; ++i) v[i] = src[(int64_t)(sp + i) * plane];
+        for (int i = 0; i < kWgradReduceDepth; ++i) v[i] = src[(int64_t)(sp + i) * plane];
+        __builtin_amdgcn_sched_barrier(0);  // (the scheduler otherwise sinks each load to its add)
 #pragma unroll
-        for (int i = 0; i < 8; ++i) s += v[i];
+        for (int i = 0; i < kWgradReduceDepth; ++i) s += v[i];
     }
-    for (; sp < P.splits; ++sp) s += src[(int64_t)sp * plane];
+    if (sp < splits) {
+        float v[kWgradReduceDepth - 1];
+#pragma unroll
+        for (int i = 0; i < kWgradReduceDepth - 1; ++i) v[i] = src[(int64_t)min(sp + i, splits - 1) * plane];
+#pragma unroll
+        for (int i = 0; i < kWgradReduceDepth - 1; ++i) {
+            const float t = s + v[i];
+            s = sp + i < splits ? t : s;
+        }
+    }
     if (n < P.N) P.grad_w[(int64_t)m * P.N + n] = s;
     else if (P.grad_b) P.grad_b[m] = s;
 }
@@ -2040,6 +2099,7 @@ int launch_wgrad(WgradBatch& wb, hipStream_t s, void* const* ev) {
         if ((rc = flush(gp[c], c, true)) || (rc = flush(g[c], c))) return rc;
     if (timed) TTAMM_HIP(hipEventRecord((hipEvent_t)ev[1], s));
     if (!narrow_first && ((rc = flush(g[0], 0)) || (rc = flush(gp[0], 0, true)))) return rc;
+    if (total > 0 && wb.tail) return launch_wgrad_tail(wb, *wb.tail, s);
     if (total > 0) {
         hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)ceil_div(total, 256)), dim3(256), 0, s, wb, total);
         TTAMM_LAUNCH_CHECK();

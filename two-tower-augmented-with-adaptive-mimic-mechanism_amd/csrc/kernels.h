@@ -142,10 +142,14 @@ struct WgradProblem {
 };
 constexpr int kMaxWgradProblems = 16;
 static_assert(kMaxWgradProblems >= 2 * (TTAMM_MAX_LINEAR + 2), "both towers: every Linear + the gate's two");
+struct WgradTail;
 struct WgradBatch {
     WgradProblem p[kMaxWgradProblems];
     int count;
     int total_blocks;
+    // host side only: when set, launch_wgrad closes with launch_wgrad_tail (the slab reduce and the
+    // AdamW update of each parameter in one kernel) instead of the plain reduce
+    const WgradTail* tail;
 };
 struct WgradShape {
     int64_t R;  // rows
@@ -779,6 +783,23 @@ struct DenseAdamArgs {
     const float* grad_scale;  // clip_grad_norm_ coefficient on the device (null: 1)
 };
 int launch_dense_adam(const DenseAdamArgs& a, hipStream_t s);
+// The one-process step's tail (optim.hip wgrad_tail_kernel): the fixed-order slab reduce of
+// launch_wgrad and launch_dense_adam's update (no grad_scale) of the same element in one thread.
+// t[i] belongs to WgradBatch::p[i]: the weight [M, N] and bias [M] with their moments.
+struct WgradTailParam {
+    float* pw;
+    float* mw;
+    float* vw;
+    float* pb;  // null: no bias
+    float* mb;
+    float* vb;
+};
+struct WgradTail {
+    WgradTailParam t[kMaxWgradProblems];
+    AdamConsts ad;
+    const uint32_t* status;  // step_poisoned(status): gradients are written, parameters untouched
+};
+int launch_wgrad_tail(const WgradBatch& wb, const WgradTail& tail, hipStream_t s);
 constexpr int kDenseSumsqBlocks = 256;
 int launch_dense_sumsq(const DenseAdamArgs& a, float* partials, hipStream_t s);
 int launch_clip_coef(const float* partials, int n, float max_norm, float* coef, hipStream_t s);

@@ -1198,6 +1198,110 @@ __global__ void dense_adam_kernel(DenseAdamArgs A, int64_t total) {
     }
 }
 
+// The one-process step's tail: wgrad_reduce_kernel and dense_adam_kernel in one pass.  A block
+// owns a 32 (n_in, the bias row n_in == N included) x 32 (m_out) tile of one problem.  Phase 1, a
+// thread per 4 consecutive m_out of a slab row: s = 0; s += slab[0]; s += slab[1]; ... per
+// element, the loads of kTailDepth splits issued before their adds (the slabs are [n_in][m_out],
+// so a wave reads whole 128-B segments).  The sums cross LDS, and phase 2 runs with n_in fastest:
+// the gradient store and the parameter's p / m / v traffic ([m_out][n_in]) are contiguous, and
+// adam_elem sees the operands dense_adam_kernel gives it.
+constexpr int kTailTile = 32, kTailDepth = 16;
+struct WgradTailArgs {
+    WgradBatch wb;
+    WgradTail tail;
+};
+static_assert(sizeof(WgradTailArgs) <= 4096, "one kernel argument");
+
+__global__ __launch_bounds__(256) void wgrad_tail_kernel(WgradTailArgs A) {
+    const KArg(WgradTailArgs)* ka = (const KArg(WgradTailArgs)*)(__builtin_amdgcn_kernarg_segment_ptr());
+    __shared__ float sums[kTailTile][kTailTile + 1];
+    int tile = blockIdx.x, pi = 0;
+    for (; pi < ka->wb.count - 1; ++pi) {
+        const int nt = ((ka->wb.p[pi].N + kTailTile) / kTailTile) * ((ka->wb.p[pi].M + kTailTile - 1) / kTailTile);
+        if (tile < nt) break;
+        tile -= nt;
+    }
+    const KArg(WgradProblem)& P = ka->wb.p[pi];
+    const KArg(WgradTailParam)& Q = ka->tail.t[pi];
+    const int Mo = P.M, Nn = P.N, splits = P.splits;
+    const int tiles_m = (Mo + kTailTile - 1) / kTailTile;
+    const int n0 = (tile / tiles_m) * kTailTile, m0 = (tile % tiles_m) * kTailTile;
+    const int64_t plane = (int64_t)(Nn + 1) * Mo;
+    const int tid = threadIdx.x;
+    {
+        const int nr = tid >> 3, mc = (tid & 7) * 4;
+        const int n = n0 + nr, m = m0 + mc;
+        f32x4_t s = {0.f, 0.f, 0.f, 0.f};  // (native vectors: the chunk stays in registers)
+        if (n <= Nn && m < Mo) {
+            const float* src = P.slab + (int64_t)n * Mo + m;
+            if ((Mo & 3) == 0 && (reinterpret_cast<uintptr_t>(P.slab) & 15) == 0) {  // m + 3 < Mo
+                int sp = 0;
+                for (; sp + kTailDepth <= splits; sp += kTailDepth) {
+                    f32x4_t v[kTailDepth];
+#pragma unroll
+                    for (int i = 0; i < kTailDepth; ++i)
+                        v[i] = *reinterpret_cast<const f32x4_t*>(src + (int64_t)(sp + i) * plane);
+                    // (the scheduler otherwise sinks each load to its add to save registers)
+                    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                    for (int i = 0; i < kTailDepth; ++i) s += v[i];
+                }
+                if (sp < splits) {  // the last partial chunk: loads past the end re-read the last split
+                    f32x4_t v[kTailDepth - 1];
+#pragma unroll
+                    for (int i = 0; i < kTailDepth - 1; ++i)
+                        v[i] = *reinterpret_cast<const f32x4_t*>(src + (int64_t)min(sp + i, splits - 1) * plane);
+#pragma unroll
+                    for (int i = 0; i < kTailDepth - 1; ++i) {
+                        const f32x4_t t = s + v[i];
+                        s = sp + i < splits ? t : s;
+                    }
+                }
+            } else {  // rows that are not 16-byte aligned: element by element
+                for (int sp = 0; sp < splits; ++sp) {
+                    const float* q = src + (int64_t)sp * plane;
+                    s.x += q[0];
+                    if (m + 1 < Mo) s.y += q[1];
+                    if (m + 2 < Mo) s.z += q[2];
+                    if (m + 3 < Mo) s.w += q[3];
+                }
+            }
+        }
+        sums[nr][mc] = s.x, sums[nr][mc + 1] = s.y, sums[nr][mc + 2] = s.z, sums[nr][mc + 3] = s.w;
+    }
+    __syncthreads();
+    const bool poisoned = step_poisoned(A.tail.status);
+    float* const gw = P.grad_w;
+    float* const gb = P.grad_b;
+    float* const pw = Q.pw;
+    float* const mw = Q.mw;
+    float* const vw = Q.vw;
+    float* const pb = Q.pb;
+    float* const mb = Q.mb;
+    float* const vb = Q.vb;
+#pragma unroll
+    for (int j = 0; j < kTailTile * kTailTile / 256; ++j) {
+        const int idx = j * 256 + tid;
+        const int nn = idx & (kTailTile - 1), mm = idx / kTailTile;
+        const int n = n0 + nn, m = m0 + mm;
+        if (n > Nn || m >= Mo) continue;
+        const float g = sums[nn][mm];
+        const bool bias = n == Nn;
+        const int64_t o = bias ? (int64_t)m : (int64_t)m * Nn + n;
+        float* gp = bias ? gb : gw;
+        float* pp = bias ? pb : pw;
+        float* pm = bias ? mb : mw;
+        float* pv = bias ? vb : vw;
+        if (gp) gp[o] = g;
+        if (poisoned || pp == nullptr) continue;
+        float p = pp[o], mo = pm[o], v = pv[o];
+        adam_elem(p, mo, v, g, A.tail.ad);
+        pp[o] = p;
+        pm[o] = mo;
+        pv[o] = v;
+    }
+}
+
 // ---- clip_grad_norm_ (training.py:824-825; torch/nn/utils/clip_grad.py) ---------------------
 // sum over a tower table pair's touched rows of |sum of the row's gradient contributions|^2
 // (the dense gradient tensor's rows; the padding row's ID gradient is zero), one thread per
@@ -1703,6 +1807,20 @@ int launch_dense_adam(const DenseAdamArgs& a, hipStream_t s) {
     for (int i = 0; i < a.count; ++i) total += a.t[i].n;
     if (total == 0) return TTAMM_OK;
     hipLaunchKernelGGL(dense_adam_kernel, dim3(grid_for(total, 256, 4096)), dim3(256), 0, s, a, total);
+    TTAMM_LAUNCH_CHECK();
+    return TTAMM_OK;
+}
+
+int launch_wgrad_tail(const WgradBatch& wb, const WgradTail& tail, hipStream_t s) {
+    WgradTailArgs a;
+    a.wb = wb;
+    a.wb.tail = nullptr;
+    a.tail = tail;
+    int64_t tiles = 0;
+    for (int i = 0; i < wb.count; ++i)
+        tiles += ceil_div(wb.p[i].N + 1, kTailTile) * ceil_div(wb.p[i].M, kTailTile);
+    if (tiles == 0) return TTAMM_OK;
+    hipLaunchKernelGGL(wgrad_tail_kernel, dim3((unsigned)tiles), dim3(256), 0, s, a);
     TTAMM_LAUNCH_CHECK();
     return TTAMM_OK;
 }

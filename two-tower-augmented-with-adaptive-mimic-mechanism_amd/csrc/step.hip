@@ -1176,8 +1176,10 @@ int rows_beside_mlp(Step& c, const StreamPlan& pl, bool single) {
     if (single && (rc = loss_finalize(c, pl.aux))) return rc;
     if ((rc = table_updates(c, c.T, c.W, 2, pl, true, A.timing_events))) return rc;
     TTAMM_HIP(hipEventRecord(pl.ev[EV_FROM_AUX], pl.aux));
-    if ((rc = tower_backward(c.T, c.W, c.D, pl.s, 2, A.timing_events + 6, BWD_MLP))) return rc;
-    if (single && (rc = dense_update(c.T, c.W, c.ad, A.status, pl.s))) return rc;
+    // single: the dense AdamW update rides in the weight gradients' slab reduce (WgradTail), the
+    // same operations per element as dense_update after the plain reduce
+    const DenseTail dense{c.ad, A.status};
+    if ((rc = tower_backward(c.T, c.W, c.D, pl.s, 2, A.timing_events + 6, BWD_MLP, single ? &dense : nullptr))) return rc;
     TTAMM_HIP(hipStreamWaitEvent(pl.s, pl.ev[EV_FROM_AUX], 0));
     return TTAMM_OK;
 }

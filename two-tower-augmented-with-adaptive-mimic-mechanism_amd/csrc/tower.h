@@ -132,8 +132,15 @@ int tower_forward(const ttamm_tower* T[2], TowerWs* W[2], const ttamm_batch& bt,
 // part BWD_GATE: the fusion's backward (dEF, the ID rows' gradient with it); BWD_MLP: the feature
 // MLP's dgrad chain and every weight gradient
 enum { BWD_GATE = 1, BWD_MLP = 2, BWD_ALL = 3 };
+// dense (optional; the one-process step without clipping): the AdamW update of every Linear
+// follows its weight gradient's slab reduce in the same kernel (kernels.h WgradTail), so the
+// caller launches no dense update
+struct DenseTail {
+    AdamConsts ad;
+    const uint32_t* status;
+};
 int tower_backward(const ttamm_tower* T[2], TowerWs* W[2], int D, hipStream_t s, int ntowers,
-                   void* const* wg_events = nullptr, int part = BWD_ALL);
+                   void* const* wg_events = nullptr, int part = BWD_ALL, const DenseTail* dense = nullptr);
 
 // Stage and range-check id segments (ids outside a table read row 0 and, with a status word, set
 // its bit), then clear and tag the claim marks of the towers that have max_norm.

@@ -608,11 +608,12 @@ bool wgrad_x16() {
 }
 
 // ---- backward ------------------------------------------------------------------------------
-int tower_wgrads(const ttamm_tower* T[2], TowerWs* W[2], int D, hipStream_t s, int ntowers, void* const* wg_events);
+int tower_wgrads(const ttamm_tower* T[2], TowerWs* W[2], int D, hipStream_t s, int ntowers, void* const* wg_events,
+                 const DenseTail* dense);
 }  // namespace
 
 int tower_backward(const ttamm_tower* T[2], TowerWs* W[2], int D, hipStream_t s, int ntowers,
-                   void* const* wg_events, int part) {
+                   void* const* wg_events, int part, const DenseTail* dense) {
     int rc;
     if (part & BWD_GATE) {
     // gate: dq, dz, dEF
@@ -731,7 +732,7 @@ int tower_backward(const ttamm_tower* T[2], TowerWs* W[2], int D, hipStream_t s,
         }
         if ((rc = bb.run(s))) return rc;
     }
-    return tower_wgrads(T, W, D, s, ntowers, wg_events);
+    return tower_wgrads(T, W, D, s, ntowers, wg_events, dense);
 }
 
 namespace {
@@ -748,10 +749,18 @@ WgradProblem wgrad_problem(const ttamm_tower& t, const TowerWs& w, const float* 
     return p;
 }
 
-// all weight gradients in one grouped launch
-int tower_wgrads(const ttamm_tower* T[2], TowerWs* W[2], int D, hipStream_t s, int ntowers, void* const* wg_events) {
+// all weight gradients in one grouped launch; dense: each Linear's AdamW update with its reduce
+int tower_wgrads(const ttamm_tower* T[2], TowerWs* W[2], int D, hipStream_t s, int ntowers, void* const* wg_events,
+                 const DenseTail* dense) {
     WgradBatch wb;
     std::memset(&wb, 0, sizeof(wb));
+    WgradTail tail;
+    std::memset(&tail, 0, sizeof(tail));
+    // the Linear whose gradient is problem wb.count (called right before the problem is added)
+    auto owner = [&](const ttamm_linear& L) {
+        tail.t[wb.count] = WgradTailParam{L.weight, L.weight_exp_avg, L.weight_exp_avg_sq,
+                                          L.bias,   L.bias_exp_avg,   L.bias_exp_avg_sq};
+    };
     for (int k = 0; k < ntowers; ++k) {
         const ttamm_tower& t = *T[k];
         TowerWs& w = *W[k];
@@ -759,12 +768,16 @@ int tower_wgrads(const ttamm_tower* T[2], TowerWs* W[2], int D, hipStream_t s, i
         float* const* gslab = w.slab + TTAMM_MAX_LINEAR;
         if (t.fusion == TTAMM_FUSION_GATED) {
             const int Hg = t.gate[0].out_features;
+            owner(t.gate[1]);
             wb.p[wb.count++] = wgrad_problem(t, w, w.dq, D, w.z, Hg, D, Hg, w.ggw[1], w.ggb[1], gslab[1]);
+            owner(t.gate[0]);
             wb.p[wb.count++] = wgrad_problem(t, w, w.dz, Hg, w.ef, 2 * D, Hg, 2 * D, w.ggw[0], w.ggb[0], gslab[0]);
         }
-        if (t.fusion == TTAMM_FUSION_CONCAT)  // dP = dT^T [e | f], db = sum dT
+        if (t.fusion == TTAMM_FUSION_CONCAT) {  // dP = dT^T [e | f], db = sum dT
+            owner(t.gate[0]);
             wb.p[wb.count++] =
                 wgrad_problem(t, w, w.dT, w.dT_ld, w.ef, efw(t), D, efw(t), w.ggw[0], w.ggb[0], gslab[0]);
+        }
         for (int l = t.n_linear - 1; l >= 0; --l) {
             const ttamm_linear& L = t.linear[l];
             const bool last = l == t.n_linear - 1;
@@ -785,8 +798,14 @@ int tower_wgrads(const ttamm_tower* T[2], TowerWs* W[2], int D, hipStream_t s, i
                     p.ld_x3 = t.feat_planes_ld;
                 }
             }
+            owner(L);
             wb.p[wb.count++] = p;
         }
+    }
+    if (dense) {
+        tail.ad = dense->ad;
+        tail.status = dense->status;
+        wb.tail = &tail;
     }
     return launch_wgrad(wb, s, wg_events);
 }
