@@ -393,7 +393,7 @@ typedef struct ttamm_step_args {
      *   built for it); anything else is TTAMM_E_INVALID.  Two passes, nothing batch x batch stored:
      *   a row log-sum-exp pass that owns the loss, then the gradient kernel.  loss_out[1] (the
      *   retrieval slot) carries the softmax mean; the mimic and category-alignment terms, clipping
-     *   and the optimizers are unchanged.  TTAMM_FP32_MFMA=exact and TTAMM_IB_KERNEL=p are not
+     *   and the optimizers are unchanged.  TTAMM_FP32_MFMA=exact is not
      *   honoured under softmax.  ttamm_eval_loss_inbatch honours the same two fields. */
     int32_t in_batch_loss;
     float in_batch_inv_temperature;
@@ -768,7 +768,7 @@ int ttamm_inbatch_bce_loss(const float* users, int64_t batch, int64_t ldu, const
  *   rejected: what ttamm_inbatch_bce rejects, and an inv_temperature that is not finite or <= 0
  *             (TTAMM_E_INVALID, before any device work).
  * Every sum has a fixed order (no float atomics): the same inputs give the same bits.  Always the
- * split-bf16 kernels: TTAMM_FP32_MFMA=exact and TTAMM_IB_KERNEL=p are not honoured. */
+ * split-bf16 kernels: TTAMM_FP32_MFMA=exact is not honoured. */
 size_t ttamm_inbatch_softmax_workspace_size(int64_t batch, int64_t n_positives, int32_t dim);
 int ttamm_inbatch_softmax(const float* users, int64_t batch, int64_t ldu, const float* positives,
                           int64_t n_positives, int64_t ldp, int32_t dim, int64_t row_base, float inv_count,

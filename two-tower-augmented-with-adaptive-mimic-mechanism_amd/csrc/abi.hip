@@ -350,7 +350,7 @@ TTAMM_API int ttamm_adamw_dense(float* param, float* exp_avg, float* exp_avg_sq,
 
 TTAMM_API size_t ttamm_inbatch_workspace_size(int64_t batch, int64_t n_positives, int32_t dim) {
     if (batch <= 0 || n_positives <= 0 || dim <= 0) return 0;
-    return inbatch_standalone_workspace_bytes(batch, n_positives, dim);
+    return inbatch_op_workspace_bytes(TTAMM_INBATCH_BCE, true, batch, n_positives, dim);
 }
 
 TTAMM_API int ttamm_inbatch_bce(const float* users, int64_t batch, int64_t ldu, const float* positives,
@@ -358,26 +358,26 @@ TTAMM_API int ttamm_inbatch_bce(const float* users, int64_t batch, int64_t ldu, 
                                 float* d_users, int64_t ld_du, float* d_positives, int64_t ld_dp, double* loss_sum,
                                 void* workspace, size_t workspace_bytes, void* stream) {
     g_last_error.clear();
-    return inbatch_standalone(users, batch, ldu, positives, n_positives, ldp, dim, row_base, inv_count, d_users,
-                              ld_du, d_positives, ld_dp, loss_sum, workspace, workspace_bytes, (hipStream_t)stream);
+    return inbatch_op(TTAMM_INBATCH_BCE, true, {users, ldu, batch, positives, ldp, n_positives, dim, row_base}, inv_count,
+                      1.0f, d_users, ld_du, d_positives, ld_dp, loss_sum, workspace, workspace_bytes, (hipStream_t)stream);
 }
 
 TTAMM_API size_t ttamm_inbatch_loss_workspace_size(int64_t batch, int64_t n_positives, int32_t dim) {
     if (batch <= 0 || n_positives <= 0 || dim <= 0) return 0;
-    return inbatch_loss_workspace_bytes(batch, n_positives, dim);
+    return inbatch_op_workspace_bytes(TTAMM_INBATCH_BCE, false, batch, n_positives, dim);
 }
 
 TTAMM_API int ttamm_inbatch_bce_loss(const float* users, int64_t batch, int64_t ldu, const float* positives,
                                      int64_t n_positives, int64_t ldp, int32_t dim, int64_t row_base,
                                      double* loss_sum, void* workspace, size_t workspace_bytes, void* stream) {
     g_last_error.clear();
-    return inbatch_loss_standalone(users, batch, ldu, positives, n_positives, ldp, dim, row_base, loss_sum, workspace,
-                                   workspace_bytes, (hipStream_t)stream);
+    return inbatch_op(TTAMM_INBATCH_BCE, false, {users, ldu, batch, positives, ldp, n_positives, dim, row_base}, 0.0f, 1.0f,
+                      nullptr, 0, nullptr, 0, loss_sum, workspace, workspace_bytes, (hipStream_t)stream);
 }
 
 TTAMM_API size_t ttamm_inbatch_softmax_workspace_size(int64_t batch, int64_t n_positives, int32_t dim) {
     if (batch <= 0 || n_positives <= 0 || dim <= 0) return 0;
-    return inbatch_softmax_workspace_bytes(batch, n_positives, dim);
+    return inbatch_op_workspace_bytes(TTAMM_INBATCH_SOFTMAX, true, batch, n_positives, dim);
 }
 
 TTAMM_API int ttamm_inbatch_softmax(const float* users, int64_t batch, int64_t ldu, const float* positives,
@@ -386,14 +386,14 @@ TTAMM_API int ttamm_inbatch_softmax(const float* users, int64_t batch, int64_t l
                                     int64_t ld_dp, double* loss_sum, void* workspace, size_t workspace_bytes,
                                     void* stream) {
     g_last_error.clear();
-    return inbatch_softmax_standalone(users, batch, ldu, positives, n_positives, ldp, dim, row_base, inv_count,
-                                      inv_temperature, d_users, ld_du, d_positives, ld_dp, loss_sum, workspace,
-                                      workspace_bytes, (hipStream_t)stream);
+    return inbatch_op(TTAMM_INBATCH_SOFTMAX, true, {users, ldu, batch, positives, ldp, n_positives, dim, row_base},
+                      inv_count, inv_temperature, d_users, ld_du, d_positives, ld_dp, loss_sum, workspace,
+                      workspace_bytes, (hipStream_t)stream);
 }
 
 TTAMM_API size_t ttamm_inbatch_softmax_loss_workspace_size(int64_t batch, int64_t n_positives, int32_t dim) {
     if (batch <= 0 || n_positives <= 0 || dim <= 0) return 0;
-    return inbatch_softmax_loss_workspace_bytes(batch, n_positives, dim);
+    return inbatch_op_workspace_bytes(TTAMM_INBATCH_SOFTMAX, false, batch, n_positives, dim);
 }
 
 TTAMM_API int ttamm_inbatch_softmax_loss(const float* users, int64_t batch, int64_t ldu, const float* positives,
@@ -401,7 +401,7 @@ TTAMM_API int ttamm_inbatch_softmax_loss(const float* users, int64_t batch, int6
                                          float inv_temperature, double* loss_sum, void* workspace,
                                          size_t workspace_bytes, void* stream) {
     g_last_error.clear();
-    return inbatch_softmax_loss_standalone(users, batch, ldu, positives, n_positives, ldp, dim, row_base,
-                                           inv_temperature, loss_sum, workspace, workspace_bytes,
-                                           (hipStream_t)stream);
+    return inbatch_op(TTAMM_INBATCH_SOFTMAX, false, {users, ldu, batch, positives, ldp, n_positives, dim, row_base}, 0.0f,
+                      inv_temperature, nullptr, 0, nullptr, 0, loss_sum, workspace, workspace_bytes,
+                      (hipStream_t)stream);
 }

@@ -193,17 +193,17 @@ static int eval_loss_run(const ttamm_step_args& A, float* logits_out, bool in_ba
     sa.partials = ws.partials;
     sa.blocks = ws.blocks;
     sa.logits = logits_out;
+    const InBatchProblem ibp = {U.aug, D, B, I.aug, D, B, D, 0};  // S = U P^T over the batch's own positives
     if (in_batch && A.in_batch_loss == TTAMM_INBATCH_SOFTMAX) {  // one LSE pass, the mean of its B terms
         InBatchLossArgs& l = ws.ib_lse;
-        l.U = U.aug, l.ldu = D, l.P = I.aug, l.ldp = D, l.D = D, l.row_base = 0;
+        static_cast<InBatchProblem&>(l) = ibp;
         if ((rc = launch_inbatch_lse(l, A.in_batch_inv_temperature, s))) return rc;
         return launch_eval_loss_inbatch_finalize(nullptr, 0, l.loss_part, inbatch_lse_parts(B), B, B, A.loss_out,
                                                  A.loss_accum, A.status, s);
     }
     if (in_batch) {
         InBatchLossArgs ib{};
-        ib.U = U.aug, ib.ldu = D, ib.B = B, ib.P = I.aug, ib.ldp = D, ib.Bc = B, ib.D = D;
-        ib.row_base = 0;
+        static_cast<InBatchProblem&>(ib) = ibp;
         ib.loss_part = ws.ib_partials;
         if ((rc = launch_inbatch_loss(ib, s))) return rc;
         sa.skip_pos = 1;

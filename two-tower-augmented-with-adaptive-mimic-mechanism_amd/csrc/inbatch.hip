@@ -22,11 +22,17 @@
 // (maximum, 1 / sum), then inbatch_x_kernel's softmax instantiation forms
 // dS = (exp(S / t - max) / sum - Y) inv_count / t = (exp(S / t - lse) - Y) inv_count / t.  Only
 // inbatch_x_kernel has a softmax form: under softmax launch_inbatch_softmax ignores
-// TTAMM_FP32_MFMA=exact and TTAMM_IB_KERNEL=p (as the forward-only BCE op ignores the former).
+// TTAMM_FP32_MFMA=exact (as the forward-only BCE op does).
+//
+// The split-bf16 kernels (inbatch_x_kernel, inbatch_loss_kernel) are built from one set of pieces:
+// ibx_row_frags (a lane's row operand), IbxStage (global -> registers -> the LDS tile image),
+// ibx_score (a 32 x 32 score block) and the ibx_exp_nabs / ibx_sigmoid / ibx_bce_* element
+// arithmetic, so the training and the validation BCE of a batch are one function of the same rows.
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
+#include <type_traits>
 
 #include "kernels.h"
 
@@ -272,9 +278,107 @@ __device__ __forceinline__ f32x16 ibx_mfma6(const bf16x8_t a[3], const bf16x8_t 
 #ifndef TTAMM_IB_SOFTMAX_PRODUCTS
 #define TTAMM_IB_SOFTMAX_PRODUCTS 6
 #endif
+// partial products of a kernel's LOSS form
+template <int LOSS>
+constexpr int kIbxProducts = LOSS == TTAMM_INBATCH_SOFTMAX ? TTAMM_IB_SOFTMAX_PRODUCTS : TTAMM_IB_PRODUCTS;
 
-// MINB blocks per CU of NW waves (32 rows each); DBUF: two LDS tile buffers (one barrier per
-// tile, the next tile split and stored right after this one's MFMAs).
+// ---- the pieces both split-bf16 kernels are made of ------------------------------------------------
+// A lane's row fragments (B operand of product 1) of half wave h: row[16 s + 8 h + j] in the three
+// planes, zero past D and where the row is past the operand's last (!row_ok: row is not read).
+template <int KS>
+__device__ __forceinline__ void ibx_row_frags(const float* row, bool row_ok, int D, int h, bf16x8_t (&rf)[KS][3]) {
+#pragma unroll
+    for (int s = 0; s < KS; ++s) {
+        const int col = 16 * s + 8 * h;
+        const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
+        const float4 a = (row_ok && col < D) ? *reinterpret_cast<const float4*>(row + col) : z;
+        const float4 b = (row_ok && col + 4 < D) ? *reinterpret_cast<const float4*>(row + col + 4) : z;
+        uint2 pa[3], pb[3];
+        ibx_split(a, pa);
+        ibx_split(b, pb);
+#pragma unroll
+        for (int q = 0; q < 3; ++q) rf[s][q] = ibx_cat(pa[q], pb[q]);
+    }
+}
+
+// A 64-row column tile on its way into LDS, staged by a block of NT threads (this one is tid) from
+// the rows of C below c_end: load() takes rows c0 .. c0 + 63 into registers (zero past c_end / D, so
+// masked rows contribute exact zeros), store() splits them into the three planes of the LDS image
+// at dst.
+template <int DP, int NT>
+struct IbxStage {
+    static constexpr int TF4 = kIbTile * DP / 4;  // float4 per column tile
+    static constexpr int LOADS = TF4 / NT;
+    static_assert(TF4 % NT == 0, "whole staging rounds");
+    const float* C;
+    int64_t ldc, c_end;
+    int D, tid;
+    float4 st[LOADS];
+
+    __device__ __forceinline__ void load(int64_t c0) {
+#pragma unroll
+        for (int it = 0; it < LOADS; ++it) {
+            const int lin = tid + it * NT;
+            const int row = lin / (DP / 4), col = (lin - row * (DP / 4)) * 4;
+            const int64_t gc = c0 + row;
+            st[it] = (gc < c_end && col < D) ? *reinterpret_cast<const float4*>(C + gc * ldc + col)
+                                             : make_float4(0.f, 0.f, 0.f, 0.f);
+        }
+    }
+    __device__ __forceinline__ void store(unsigned char* dst) const {
+#pragma unroll
+        for (int it = 0; it < LOADS; ++it) {
+            const int lin = tid + it * NT;
+            const int row = lin / (DP / 4), c4 = lin - row * (DP / 4);
+            const int o = ibx_off(row, c4 >> 1) + 8 * (c4 & 1);
+            uint2 pl[3];
+            ibx_split(st[it], pl);
+#pragma unroll
+            for (int q = 0; q < 3; ++q) *reinterpret_cast<uint2*>(dst + q * kIbxPlane + o) = pl[q];
+        }
+    }
+};
+
+// Product 1: the S^T block [32 c x 32 u] of tile rows 32 jc .. 32 jc + 31 against the wave's rows
+// (lane: row u = li of half wave h; register r: tile column 32 jc + (r & 3) + 8 (r >> 2) + 4 h).
+template <int NP, int KS>
+__device__ __forceinline__ f32x16 ibx_score(const unsigned char* tile, int jc, int li, int h,
+                                            const bf16x8_t (&rf)[KS][3]) {
+    f32x16 s2;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) s2[r] = 0.f;
+#pragma unroll
+    for (int s = 0; s < KS; ++s) {
+        const int o = ibx_off(32 * jc + li, 2 * s + h);
+        bf16x8_t a[3];
+#pragma unroll
+        for (int q = 0; q < 3; ++q) a[q] = *reinterpret_cast<const bf16x8_t*>(tile + q * kIbxPlane + o);
+        s2 = ibx_mfma6<NP>(a, rf[s], s2);
+    }
+    return s2;
+}
+
+// The element arithmetic on hardware exp2 / log2 / rcp (<= 1-2 ulp): the elementwise pass, not the
+// MFMAs, bounds the kernels with IEEE expf / logf / division.  Sigmoid and the ATen BCE term from
+// one exp: t = exp(-|x|); for x >= 0 exp(-max(-x,0)) = 1 and exp(-x-max(-x,0)) = t, for x < 0 the
+// reverse.
+__device__ __forceinline__ float ibx_exp_nabs(float x) { return __builtin_amdgcn_exp2f(-fabsf(x) * 1.4426950408889634f); }
+__device__ __forceinline__ float ibx_sigmoid(float x, float t) {
+    const float inv = __builtin_amdgcn_rcpf(1.0f + t);
+    return x >= 0.f ? inv : t * inv;
+}
+// label-free (y = 0): the term is max(x, 0) + ln(1 + t) (x + max(-x, 0) == max(x, 0) exactly), kept
+// as two lane sums (the log2 terms are scaled by ln 2 once at the end)
+__device__ __forceinline__ void ibx_bce_free(float x, float t, float& lin, float& lg2) {
+    lin += fmaxf(x, 0.f);
+    lg2 += __builtin_amdgcn_logf(1.0f + t);
+}
+// the term under label y
+__device__ __forceinline__ float ibx_bce_term(float x, float y, float t) {
+    return (1.0f - y) * x + fmaxf(-x, 0.f) + __builtin_amdgcn_logf(1.0f + t) * 0.6931471805599453f;
+}
+
+// 4 waves (32 rows each), two blocks per CU.
 // LOSS (compile time; the BCE code is the same with or without the softmax branch):
 //   TTAMM_INBATCH_BCE      dS = (sigmoid(S) - Y) * inv_T, the BCE terms summed into loss_part;
 //   TTAMM_INBATCH_SOFTMAX  dS = (exp2(S * z_scale - rmax) * rinv - Y) * inv_T with the rows' (rmax,
@@ -284,21 +388,19 @@ __device__ __forceinline__ f32x16 ibx_mfma6(const bf16x8_t a[3], const bf16x8_t 
 //     consecutive tile columns; every lane of a half wave reads one address: a broadcast).  inv_T
 //     multiplies the accumulators once at the slab write, not every element.  No loss is
 //     accumulated: the LSE pass owns it.
-template <int DP, int MINB, int NW, bool DBUF, int LOSS = TTAMM_INBATCH_BCE>
-__global__ __launch_bounds__(64 * NW, MINB) void inbatch_x_kernel(InBatchArgs A) {
+template <int DP, int LOSS = TTAMM_INBATCH_BCE>
+__global__ __launch_bounds__(2 * kIbRows, 2) void inbatch_x_kernel(InBatchArgs A) {
+    constexpr int NW = kIbRows / 32;                 // waves
     constexpr int NT = 64 * NW;                      // threads
     constexpr int NB = DP / 32;                      // 32-wide output column blocks
     constexpr int KS = DP / 16;                      // k steps of product 1
-    constexpr int TF4 = kIbTile * DP / 4;            // float4 per column tile
-    constexpr int LOADS = TF4 / NT;
     constexpr bool SOFTMAX = LOSS == TTAMM_INBATCH_SOFTMAX;
-    constexpr int NP = SOFTMAX ? TTAMM_IB_SOFTMAX_PRODUCTS : TTAMM_IB_PRODUCTS;  // partial products
-    static_assert(TF4 % NT == 0, "whole staging rounds");
+    constexpr int NP = kIbxProducts<LOSS>;
     static_assert(NT >= 2 * kIbTile, "one thread per staged rmax / rinv");
-    __shared__ __attribute__((aligned(16))) unsigned char tiles[DBUF ? 2 : 1][3 * kIbxPlane];
+    __shared__ __attribute__((aligned(16))) unsigned char tile[3 * kIbxPlane];
     __shared__ float red[NW];
-    // [buffer][rmax | rinv][tile column]
-    __shared__ __attribute__((aligned(16))) float nrm_t[SOFTMAX ? (DBUF ? 2 : 1) : 1][2][SOFTMAX ? kIbTile : 2];
+    // [rmax | rinv][tile column]
+    __shared__ __attribute__((aligned(16))) float nrm_t[2][SOFTMAX ? kIbTile : 2];
 
     int blk = blockIdx.x;
     const int nu = A.rblk_u * A.splits_u;
@@ -315,26 +417,10 @@ __global__ __launch_bounds__(64 * NW, MINB) void inbatch_x_kernel(InBatchArgs A)
     const int D = A.D;
 
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, li = lane & 31, h = lane >> 5;
-    const int64_t r0 = (int64_t)rb * (32 * NW) + 32 * w;
+    const int64_t r0 = (int64_t)rb * kIbRows + 32 * w;
 
-    // this lane's row fragments (B operand of product 1): R[r0 + li][16 s + 8 h + j], zero past D / nr
     bf16x8_t rf[KS][3];
-    {
-        const int64_t row = r0 + li;
-        const bool rok = row < nr;
-#pragma unroll
-        for (int s = 0; s < KS; ++s) {
-            const int col = 16 * s + 8 * h;
-            const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
-            const float4 a = (rok && col < D) ? *reinterpret_cast<const float4*>(R + row * ldr + col) : z;
-            const float4 b = (rok && col + 4 < D) ? *reinterpret_cast<const float4*>(R + row * ldr + col + 4) : z;
-            uint2 pa[3], pb[3];
-            ibx_split(a, pa);
-            ibx_split(b, pb);
-#pragma unroll
-            for (int q = 0; q < 3; ++q) rf[s][q] = ibx_cat(pa[q], pb[q]);
-        }
-    }
+    ibx_row_frags(R + (r0 + li) * ldr, r0 + li < nr, D, h, rf);
     f32x16 acc[NB];
 #pragma unroll
     for (int n = 0; n < NB; ++n)
@@ -342,30 +428,7 @@ __global__ __launch_bounds__(64 * NW, MINB) void inbatch_x_kernel(InBatchArgs A)
         for (int r = 0; r < 16; ++r) acc[n][r] = 0.f;
     float bce = 0.f, bce_lin = 0.f, bce_log2 = 0.f;
 
-    // column tile -> registers (zero past c_end / D, so masked rows contribute exact zeros)
-    float4 st[LOADS];
-    auto load = [&](int64_t c0) {
-#pragma unroll
-        for (int it = 0; it < LOADS; ++it) {
-            const int lin = tid + it * NT;
-            const int row = lin / (DP / 4), col = (lin - row * (DP / 4)) * 4;
-            const int64_t gc = c0 + row;
-            st[it] = (gc < c_end && col < D) ? *reinterpret_cast<const float4*>(C + gc * ldc + col)
-                                             : make_float4(0.f, 0.f, 0.f, 0.f);
-        }
-    };
-    auto store = [&](unsigned char* dst) {
-#pragma unroll
-        for (int it = 0; it < LOADS; ++it) {
-            const int lin = tid + it * NT;
-            const int row = lin / (DP / 4), c4 = lin - row * (DP / 4);
-            const int o = ibx_off(row, c4 >> 1) + 8 * (c4 & 1);
-            uint2 pl[3];
-            ibx_split(st[it], pl);
-#pragma unroll
-            for (int q = 0; q < 3; ++q) *reinterpret_cast<uint2*>(dst + q * kIbxPlane + o) = pl[q];
-        }
-    };
+    IbxStage<DP, NT> stage{C, ldc, c_end, D, tid};
     // softmax: the user role's row (rmax, rinv) in two registers; the item role's tile columns are
     // users, whose pairs travel with the tile (threads 0..63 rmax, 64..127 rinv; zero past c_end:
     // those elements are masked)
@@ -373,57 +436,34 @@ __global__ __launch_bounds__(64 * NW, MINB) void inbatch_x_kernel(InBatchArgs A)
     float max_r = 0.f, inv_r = 0.f, st_l = 0.f;
     if constexpr (SOFTMAX)
         if (role_u && gr < nr) max_r = A.rmax[gr], inv_r = A.rinv[gr];
-    auto load_lse = [&](int64_t c0) {
+    auto load = [&](int64_t c0) {
+        stage.load(c0);
         if constexpr (SOFTMAX)
             if (!role_u && tid < 2 * kIbTile) {
                 const int64_t u = c0 + (tid & (kIbTile - 1));
                 st_l = u < c_end ? (tid < kIbTile ? A.rmax[u] : A.rinv[u]) : 0.f;
             }
     };
-    auto store_lse = [&](int buf) {
+    auto store = [&] {
+        stage.store(tile);
         if constexpr (SOFTMAX)
-            if (!role_u && tid < 2 * kIbTile) nrm_t[buf][tid >> 6][tid & (kIbTile - 1)] = st_l;
+            if (!role_u && tid < 2 * kIbTile) nrm_t[tid >> 6][tid & (kIbTile - 1)] = st_l;
     };
 
     const int ntiles = c_end > c_begin ? (int)((c_end - c_begin + kIbTile - 1) / kIbTile) : 0;
     // the next tile in flight in registers while this one is multiplied (narrow D); at D > 64 the
     // registers go to the operands and the second block of the CU hides the load instead
-    constexpr bool PREFETCH = DP <= 64 || MINB == 1;
-    if (DBUF) {  // tile 0 in buffer 0, tile 1 in flight in registers
-        if (ntiles > 0) {
-            load(c_begin);
-            load_lse(c_begin);
-            store(tiles[0]);
-            store_lse(0);
-            if (ntiles > 1) {
-                load(c_begin + kIbTile);
-                load_lse(c_begin + kIbTile);
-            }
-        }
-        __syncthreads();
-    } else if (PREFETCH && ntiles > 0) {
-        load(c_begin);
-        load_lse(c_begin);
-    }
+    constexpr bool PREFETCH = DP <= 64;
+    if (PREFETCH && ntiles > 0) load(c_begin);
     // tr-read lane roles: 16-lane group g, lane 4q + p of the group
     const int g = lane >> 4, q4 = (lane >> 2) & 3, p4 = lane & 3;
     for (int t = 0; t < ntiles; ++t) {
         const int64_t c0 = c_begin + (int64_t)t * kIbTile;
-        unsigned char* const tile = tiles[DBUF ? (t & 1) : 0];
-        if (!DBUF) {
-            if (!PREFETCH) {
-                load(c0);
-                load_lse(c0);
-            }
-            __syncthreads();  // every wave is done with the previous tile
-            store(tile);
-            store_lse(0);
-            __syncthreads();
-            if (PREFETCH && t + 1 < ntiles) {  // in flight during this tile's MFMAs
-                load(c0 + kIbTile);
-                load_lse(c0 + kIbTile);
-            }
-        }
+        if (!PREFETCH) load(c0);
+        __syncthreads();  // every wave is done with the previous tile
+        store();
+        __syncthreads();
+        if (PREFETCH && t + 1 < ntiles) load(c0 + kIbTile);  // in flight during this tile's MFMAs
         // the label Y = 1 sits at tile column diag of this lane's row: user u's own positive is
         // column row_base + u (user role), positive i's user is row i - row_base (item role)
         const int64_t dl = role_u ? A.row_base + gr - c0 : gr - A.row_base - c0;
@@ -434,23 +474,8 @@ __global__ __launch_bounds__(64 * NW, MINB) void inbatch_x_kernel(InBatchArgs A)
         const bool fast = cols_here == kIbTile && __builtin_amdgcn_ballot_w64(diag >= 0 || !row_ok) == 0;
 #pragma unroll
         for (int jc = 0; jc < 2; ++jc) {  // tile rows 32 jc .. 32 jc + 31
-            // ---- product 1: S^T block [32 c x 32 u] --------------------------------------------------
-            f32x16 s2;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) s2[r] = 0.f;
-#pragma unroll
-            for (int s = 0; s < KS; ++s) {
-                const int o = ibx_off(32 * jc + li, 2 * s + h);
-                bf16x8_t a[3];
-#pragma unroll
-                for (int q = 0; q < 3; ++q) a[q] = *reinterpret_cast<const bf16x8_t*>(tile + q * kIbxPlane + o);
-                s2 = ibx_mfma6<NP>(a, rf[s], s2);
-            }
+            f32x16 s2 = ibx_score<NP>(tile, jc, li, h, rf);
             // ---- dS^T in registers (lane: row u = r0 + li; register r: tile column c) -----------
-            // hardware exp2 / log2 / rcp (<= 1-2 ulp): this elementwise pass, not the MFMAs, bounds
-            // the kernel with IEEE expf / logf / division.  Sigmoid and the ATen BCE term from one
-            // exp: t = exp(-|x|); for x >= 0 exp(-max(-x,0)) = 1 and exp(-x-max(-x,0)) = t, for x < 0
-            // the reverse.
             if constexpr (SOFTMAX) {
                 // softmax: p = exp2(x z_scale - rmax) rinv (one fma, one hardware exp2, one multiply),
                 // dS / inv_T = p - y; the interior fast path has no y and no range tests
@@ -459,9 +484,9 @@ __global__ __launch_bounds__(64 * NW, MINB) void inbatch_x_kernel(InBatchArgs A)
                 for (int q = 0; q < 4; ++q) {  // registers 4 q .. 4 q + 3: four consecutive tile columns
                     float4 m4, i4;
                     if (!role_u) {
-                        const float* nt = nrm_t[DBUF ? (t & 1) : 0][0] + 32 * jc + 4 * h + 8 * q;
+                        const float* nt = nrm_t[0] + 32 * jc + 4 * h + 8 * q;
                         m4 = *reinterpret_cast<const float4*>(nt);
-                        i4 = *reinterpret_cast<const float4*>(nt + (SOFTMAX ? kIbTile : 2));
+                        i4 = *reinterpret_cast<const float4*>(nt + kIbTile);
                     } else {
                         m4 = make_float4(max_r, max_r, max_r, max_r);
                         i4 = make_float4(inv_r, inv_r, inv_r, inv_r);
@@ -482,29 +507,22 @@ __global__ __launch_bounds__(64 * NW, MINB) void inbatch_x_kernel(InBatchArgs A)
                     }
                 }
             } else if (fast) {
-                // every row and column in range, no label in this wave's block: y = 0, so the BCE
-                // term is max(x, 0) + ln(1 + t) (x + max(-x, 0) == max(x, 0) exactly), summed as
-                // two lane sums (the log2 terms scaled by ln 2 once at the end)
+                // every row and column in range, no label in this wave's block: y = 0 (the BCE terms
+                // are the user role's)
                 if (role_u) {
 #pragma unroll
                     for (int r = 0; r < 16; ++r) {
                         const float x = s2[r];
-                        const float tx = __builtin_amdgcn_exp2f(-fabsf(x) * 1.4426950408889634f);
-                        const float d1 = 1.0f + tx;
-                        const float inv = __builtin_amdgcn_rcpf(d1);
-                        const float sg = x >= 0.f ? inv : tx * inv;
-                        bce_lin += fmaxf(x, 0.f);
-                        bce_log2 += __builtin_amdgcn_logf(d1);
+                        const float tx = ibx_exp_nabs(x);
+                        const float sg = ibx_sigmoid(x, tx);
+                        ibx_bce_free(x, tx, bce_lin, bce_log2);
                         s2[r] = sg * A.inv_T;
                     }
                 } else {
 #pragma unroll
                     for (int r = 0; r < 16; ++r) {
                         const float x = s2[r];
-                        const float tx = __builtin_amdgcn_exp2f(-fabsf(x) * 1.4426950408889634f);
-                        const float inv = __builtin_amdgcn_rcpf(1.0f + tx);
-                        const float sg = x >= 0.f ? inv : tx * inv;
-                        s2[r] = sg * A.inv_T;
+                        s2[r] = ibx_sigmoid(x, ibx_exp_nabs(x)) * A.inv_T;
                     }
                 }
             } else {
@@ -514,10 +532,9 @@ __global__ __launch_bounds__(64 * NW, MINB) void inbatch_x_kernel(InBatchArgs A)
                     const bool ok = row_ok && lc < cols_here;
                     const float y = lc == diag ? 1.0f : 0.0f;
                     const float x = s2[r];
-                    const float tx = __builtin_amdgcn_exp2f(-fabsf(x) * 1.4426950408889634f);
-                    const float inv = __builtin_amdgcn_rcpf(1.0f + tx);
-                    const float sg = x >= 0.f ? inv : tx * inv;
-                    if (role_u && ok) bce += (1.0f - y) * x + fmaxf(-x, 0.f) + __builtin_amdgcn_logf(1.0f + tx) * 0.6931471805599453f;
+                    const float tx = ibx_exp_nabs(x);
+                    const float sg = ibx_sigmoid(x, tx);
+                    if (role_u && ok) bce += ibx_bce_term(x, y, tx);
                     s2[r] = ok ? (sg - y) * A.inv_T : 0.f;
                 }
             }
@@ -552,19 +569,6 @@ __global__ __launch_bounds__(64 * NW, MINB) void inbatch_x_kernel(InBatchArgs A)
                 }
             }
         }
-        if (DBUF) {
-            // tile t + 1 (landed in registers during this tile's MFMAs) into the other buffer, last
-            // read in tile t - 1 before that tile's barrier; tile t + 2 in flight
-            if (t + 1 < ntiles) {
-                store(tiles[(t + 1) & 1]);
-                store_lse((t + 1) & 1);
-                if (t + 2 < ntiles) {
-                    load(c0 + 2 * kIbTile);
-                    load_lse(c0 + 2 * kIbTile);
-                }
-            }
-            __syncthreads();
-        }
     }
     // ---- partial rows -> this split's slab ------------------------------------------------------
     float* slab = role_u ? A.slab_u + (int64_t)sp * A.B * D : A.slab_p + (int64_t)sp * A.Bc * D;
@@ -590,295 +594,6 @@ __global__ __launch_bounds__(64 * NW, MINB) void inbatch_x_kernel(InBatchArgs A)
     }
 }
 
-// ---- software-pipelined variant (default): one wave per SIMD ---------------------------------------
-// The split kernel above at two waves per SIMD spills at D = 128 (the row fragments, 96 registers,
-// and the dR accumulators, 64, leave too little of a 256-register budget), and its VALU work (the
-// sigmoid / BCE pass and the dS splits) only overlaps the MFMAs across the two waves.  Here one
-// 256-thread block per CU (one wave per SIMD, up to 512 registers: no spills) runs each role in a
-// launch of its own (ROLE_U compile-time: the BCE terms only in the user role's code) and pipelines
-// a 64-column tile inside the wave, in one basic block per tile:
-//   S1 = P1(cols 0..31);  S2 = P1(cols 32..63)  ||  dS(S1);  P2(S1)  ||  dS(S2);  P2(S2)  ||  next tile -> LDS
-// so the 8-cycle-issue MFMAs of one product cover the elementwise VALU of the other half.  The
-// column tile is double buffered in LDS (one barrier per tile), the tile after next in flight in
-// registers.  Same roles, splits, slabs, operand images and arithmetic as inbatch_x_kernel.
-#ifndef IB_VALU_PER_MFMA
-#define IB_VALU_PER_MFMA 5
-#endif
-template <int DP, bool ROLE_U>
-__global__ __launch_bounds__(256, 1) void inbatch_p_kernel(InBatchArgs A) {
-    constexpr int NB = DP / 32;
-    constexpr int KS = DP / 16;
-    constexpr int TF4 = kIbTile * DP / 4;
-    constexpr int LOADS = TF4 / 256;
-    static_assert(TF4 % 256 == 0, "whole staging rounds");
-    __shared__ __attribute__((aligned(16))) unsigned char tiles[2][3 * kIbxPlane];
-    __shared__ float red[4];
-
-    const int blk = blockIdx.x;
-    const int splits = ROLE_U ? A.splits_u : A.splits_p;
-    const int rb = blk / splits, sp = blk - (blk / splits) * splits;
-    const float* R = ROLE_U ? A.U : A.P;
-    const int64_t ldr = ROLE_U ? A.ldu : A.ldp, nr = ROLE_U ? A.B : A.Bc;
-    const float* C = ROLE_U ? A.P : A.U;
-    const int64_t ldc = ROLE_U ? A.ldp : A.ldu, nc = ROLE_U ? A.Bc : A.B;
-    const int64_t per = ROLE_U ? A.cols_u : A.cols_p;
-    const int64_t c_begin = min(nc, (int64_t)sp * per), c_end = min(nc, c_begin + per);
-    const int D = A.D;
-    const float inv_T = A.inv_T;
-
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, li = lane & 31, h = lane >> 5;
-    const int64_t r0 = (int64_t)rb * kIbRows + 32 * w;
-
-    bf16x8_t rf[KS][3];
-    {
-        const int64_t row = r0 + li;
-        const bool rok = row < nr;
-#pragma unroll
-        for (int s = 0; s < KS; ++s) {
-            const int col = 16 * s + 8 * h;
-            const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
-            const float4 a = (rok && col < D) ? *reinterpret_cast<const float4*>(R + row * ldr + col) : z;
-            const float4 b = (rok && col + 4 < D) ? *reinterpret_cast<const float4*>(R + row * ldr + col + 4) : z;
-            uint2 pa[3], pb[3];
-            ibx_split(a, pa);
-            ibx_split(b, pb);
-#pragma unroll
-            for (int q = 0; q < 3; ++q) rf[s][q] = ibx_cat(pa[q], pb[q]);
-        }
-    }
-    f32x16 acc[NB];
-#pragma unroll
-    for (int n = 0; n < NB; ++n)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[n][r] = 0.f;
-    float bce = 0.f, bce_lin = 0.f, bce_log2 = 0.f;
-
-    float4 st[LOADS];
-    auto load = [&](int64_t c0) {
-#pragma unroll
-        for (int it = 0; it < LOADS; ++it) {
-            const int lin = tid + it * 256;
-            const int row = lin / (DP / 4), col = (lin - row * (DP / 4)) * 4;
-            const int64_t gc = c0 + row;
-            st[it] = (gc < c_end && col < D) ? *reinterpret_cast<const float4*>(C + gc * ldc + col)
-                                             : make_float4(0.f, 0.f, 0.f, 0.f);
-        }
-    };
-    auto store = [&](unsigned char* dst) {
-#pragma unroll
-        for (int it = 0; it < LOADS; ++it) {
-            const int lin = tid + it * 256;
-            const int row = lin / (DP / 4), c4 = lin - row * (DP / 4);
-            const int o = ibx_off(row, c4 >> 1) + 8 * (c4 & 1);
-            uint2 pl[3];
-            ibx_split(st[it], pl);
-#pragma unroll
-            for (int q = 0; q < 3; ++q) *reinterpret_cast<uint2*>(dst + q * kIbxPlane + o) = pl[q];
-        }
-    };
-    const int g = lane >> 4, q4 = (lane >> 2) & 3, p4 = lane & 3;
-    const int64_t gr = r0 + li;
-    const bool row_ok = gr < nr;
-
-    // product 1: S^T block of tile rows 32 jc .. 32 jc + 31 x this wave's 32 rows
-    auto p1 = [&](const unsigned char* tile, int jc) {
-        f32x16 s2;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) s2[r] = 0.f;
-#pragma unroll
-        for (int s = 0; s < KS; ++s) {
-            const int o = ibx_off(32 * jc + li, 2 * s + h);
-            bf16x8_t a[3];
-#pragma unroll
-            for (int q = 0; q < 3; ++q) a[q] = *reinterpret_cast<const bf16x8_t*>(tile + q * kIbxPlane + o);
-            s2 = ibx_mfma6(a, rf[s], s2);
-        }
-        return s2;
-    };
-    // dS^T in registers: the label-free interior form, or the general one (labels, edges)
-    auto ds_general = [&](f32x16& s2, int jc, int diag, int cols_here) {
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int lc = 32 * jc + (r & 3) + 8 * (r >> 2) + 4 * h;
-            const bool ok = row_ok && lc < cols_here;
-            const float y = lc == diag ? 1.0f : 0.0f;
-            const float x = s2[r];
-            const float tx = __builtin_amdgcn_exp2f(-fabsf(x) * 1.4426950408889634f);
-            const float inv = __builtin_amdgcn_rcpf(1.0f + tx);
-            const float sg = x >= 0.f ? inv : tx * inv;
-            if (ROLE_U && ok) bce += (1.0f - y) * x + fmaxf(-x, 0.f) + __builtin_amdgcn_logf(1.0f + tx) * 0.6931471805599453f;
-            s2[r] = ok ? (sg - y) * inv_T : 0.f;
-        }
-    };
-    // product 2: acc[n] += dS . tile rows 32 jc ..
-    auto p2 = [&](const unsigned char* tile, const f32x16& s2, int jc) {
-#pragma unroll
-        for (int s = 0; s < 2; ++s) {
-            bf16x8_t a[3];
-            {
-                const float4 x0 = make_float4(s2[8 * s + 0], s2[8 * s + 1], s2[8 * s + 2], s2[8 * s + 3]);
-                const float4 x1 = make_float4(s2[8 * s + 4], s2[8 * s + 5], s2[8 * s + 6], s2[8 * s + 7]);
-                uint2 pa[3], pb[3];
-                ibx_split(x0, pa);
-                ibx_split(x1, pb);
-#pragma unroll
-                for (int q = 0; q < 3; ++q) a[q] = ibx_cat(pa[q], pb[q]);
-            }
-            const int brow = 32 * jc + 16 * s + 4 * h + q4;
-#pragma unroll
-            for (int n = 0; n < NB; ++n) {
-                const int ch = 4 * n + 2 * (g & 1) + (p4 >> 1);
-                const int o0 = ibx_off(brow, ch) + 8 * (p4 & 1), o1 = ibx_off(brow + 8, ch) + 8 * (p4 & 1);
-                bf16x8_t b[3];
-#pragma unroll
-                for (int q = 0; q < 3; ++q) {
-                    const s16x4_t lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_t*)(tile + q * kIbxPlane + o0));
-                    const s16x4_t hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_t*)(tile + q * kIbxPlane + o1));
-                    const s16x8_t v = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-                    b[q] = __builtin_bit_cast(bf16x8_t, v);
-                }
-                acc[n] = ibx_mfma6(a, b, acc[n]);
-            }
-        }
-    };
-
-    // one element of ds_fast (the interleaved form; same operations)
-    auto ds_fast_elem = [&](f32x16& s2, int r) {
-        const float x = s2[r];
-        const float tx = __builtin_amdgcn_exp2f(-fabsf(x) * 1.4426950408889634f);
-        const float d1 = 1.0f + tx;
-        const float inv = __builtin_amdgcn_rcpf(d1);
-        const float sg = x >= 0.f ? inv : tx * inv;
-        if (ROLE_U) {
-            bce_lin += fmaxf(x, 0.f);
-            bce_log2 += __builtin_amdgcn_logf(d1);
-        }
-        s2[r] = sg * inv_T;
-    };
-    // staging round i (of LOADS) of the next tile: its three planes into dst
-    auto store_part = [&](unsigned char* dst, int it) {
-        if (it >= LOADS) return;
-        const int lin = tid + it * 256;
-        const int row = lin / (DP / 4), c4 = lin - row * (DP / 4);
-        const int o = ibx_off(row, c4 >> 1) + 8 * (c4 & 1);
-        uint2 pl[3];
-        ibx_split(st[it], pl);
-#pragma unroll
-        for (int q = 0; q < 3; ++q) *reinterpret_cast<uint2*>(dst + q * kIbxPlane + o) = pl[q];
-    };
-    // product 2 with side work f(i) after its i-th 6-MFMA group (i = 0 .. 2 NB - 1); the staging
-    // rounds past 2 NB (LOADS > 2 NB) run after the last group
-    auto split8 = [&](const f32x16& s2, int s, bf16x8_t a[3]) {
-        const float4 x0 = make_float4(s2[8 * s + 0], s2[8 * s + 1], s2[8 * s + 2], s2[8 * s + 3]);
-        const float4 x1 = make_float4(s2[8 * s + 4], s2[8 * s + 5], s2[8 * s + 6], s2[8 * s + 7]);
-        uint2 pa[3], pb[3];
-        ibx_split(x0, pa);
-        ibx_split(x1, pb);
-#pragma unroll
-        for (int q = 0; q < 3; ++q) a[q] = ibx_cat(pa[q], pb[q]);
-    };
-    auto p2_il = [&](const unsigned char* tile, const f32x16& s2, int jc, auto&& f) {
-        bf16x8_t aa[2][3];
-        split8(s2, 0, aa[0]);
-#pragma unroll
-        for (int s = 0; s < 2; ++s) {
-            const bf16x8_t* a = aa[s];
-            const int brow = 32 * jc + 16 * s + 4 * h + q4;
-#pragma unroll
-            for (int n = 0; n < NB; ++n) {
-                const int ch = 4 * n + 2 * (g & 1) + (p4 >> 1);
-                const int o0 = ibx_off(brow, ch) + 8 * (p4 & 1), o1 = ibx_off(brow + 8, ch) + 8 * (p4 & 1);
-                bf16x8_t b[3];
-#pragma unroll
-                for (int q = 0; q < 3; ++q) {
-                    const s16x4_t lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_t*)(tile + q * kIbxPlane + o0));
-                    const s16x4_t hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_t*)(tile + q * kIbxPlane + o1));
-                    const s16x8_t v = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-                    b[q] = __builtin_bit_cast(bf16x8_t, v);
-                }
-                acc[n] = ibx_mfma6(a, b, acc[n]);
-                if (s == 0 && n == 0) split8(s2, 1, aa[1]);  // the second half's planes under these MFMAs
-                f(s * NB + n);
-            }
-        }
-    };
-
-    const int ntiles = c_end > c_begin ? (int)((c_end - c_begin + kIbTile - 1) / kIbTile) : 0;
-    if (ntiles > 0) {
-        load(c_begin);
-        store(tiles[0]);
-        if (ntiles > 1) load(c_begin + kIbTile);
-    }
-    __syncthreads();
-    for (int t = 0; t < ntiles; ++t) {
-        const int64_t c0 = c_begin + (int64_t)t * kIbTile;
-        const unsigned char* const tile = tiles[t & 1];
-        unsigned char* const next = tiles[(t + 1) & 1];
-        const bool more = t + 1 < ntiles;
-        const int64_t dl = ROLE_U ? A.row_base + gr - c0 : gr - A.row_base - c0;
-        const int diag = (dl >= 0 && dl < kIbTile) ? (int)dl : -1;
-        const int cols_here = (int)min((int64_t)kIbTile, c_end - c0);
-        const bool fast = cols_here == kIbTile && __builtin_amdgcn_ballot_w64(diag >= 0 || !row_ok) == 0;
-        // tile t + 1 goes into the other buffer (last read in tile t - 1, before that tile's
-        // barrier; after the last tile the store is harmless), tile t + 2 into flight (masked to
-        // zeros past the split's columns) — unconditionally, so each body is one basic block
-        (void)more;
-        if (fast) {
-            // written in issue order: every MFMA group of one product carries a slice of the
-            // other half's elementwise work
-            f32x16 s_a = p1(tile, 0);
-            f32x16 s_b;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) s_b[r] = 0.f;
-            // S(cols 32..63) || dS(cols 0..31), two elements per k-step
-#pragma unroll
-            for (int ks = 0; ks < KS; ++ks) {
-                const int o = ibx_off(32 + li, 2 * ks + h);
-                bf16x8_t a[3];
-#pragma unroll
-                for (int q = 0; q < 3; ++q) a[q] = *reinterpret_cast<const bf16x8_t*>(tile + q * kIbxPlane + o);
-                s_b = ibx_mfma6(a, rf[ks], s_b);
-#pragma unroll
-                for (int e = (ks * 16) / KS; e < ((ks + 1) * 16) / KS; ++e) ds_fast_elem(s_a, e);
-            }
-            // dR += dS(cols 0..31) . tile || dS(cols 32..63), 16 / (2 NB) elements per 6-MFMA group
-            p2_il(tile, s_a, 0, [&](int i) {
-#pragma unroll
-                for (int e = (i * 16) / (2 * NB); e < ((i + 1) * 16) / (2 * NB); ++e) ds_fast_elem(s_b, e);
-            });
-            // dR += dS(cols 32..63) . tile || the next tile's planes into the other buffer
-            p2_il(tile, s_b, 1, [&](int i) { store_part(next, i); });
-            load(c0 + 2 * kIbTile);
-        } else {
-            f32x16 s_a = p1(tile, 0);
-            f32x16 s_b = p1(tile, 1);
-            ds_general(s_a, 0, diag, cols_here);
-            p2(tile, s_a, 0);
-            ds_general(s_b, 1, diag, cols_here);
-            p2(tile, s_b, 1);
-            store(next);
-            load(c0 + 2 * kIbTile);
-        }
-        __syncthreads();
-    }
-    float* slab = ROLE_U ? A.slab_u + (int64_t)sp * A.B * D : A.slab_p + (int64_t)sp * A.Bc * D;
-#pragma unroll
-    for (int n = 0; n < NB; ++n)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int lr = (r & 3) + 8 * (r >> 2) + 4 * h;
-            const int64_t grr = r0 + lr;
-            const int col = 32 * n + li;
-            if (grr < nr && col < D) slab[grr * D + col] = acc[n][r];
-        }
-    if (ROLE_U) {
-        bce = wave_sum(bce + (bce_lin + bce_log2 * 0.6931471805599453f));
-        if (lane == 0) red[w] = bce;
-        __syncthreads();
-        if (tid == 0) A.loss_part[blk] = (red[0] + red[1]) + (red[2] + red[3]);
-    }
-}
-
 // dU = sum of the user slabs, dP = sum of the item slabs, in split order.
 __global__ void ib_reduce_kernel(InBatchArgs A) {
     const int64_t nu = A.B * A.D, total = nu + A.Bc * A.D;
@@ -897,8 +612,8 @@ __global__ void ib_reduce_kernel(InBatchArgs A) {
     }
 }
 
-// The BCE sum over the user-role blocks' partial sums, in block order (fp64 accumulation):
-// the standalone entry's loss (the fused step folds the parts into loss_finalize_kernel).
+// A loss sum over blocks' partial sums, in block order (fp64 accumulation): the one-op entries'
+// loss (the fused step folds the parts into loss_finalize_kernel).
 __global__ void ib_loss_sum_kernel(const float* __restrict__ parts, int n, double* __restrict__ out) {
     __shared__ double red[256];
     double s = 0.0;
@@ -915,12 +630,12 @@ __global__ void ib_loss_sum_kernel(const float* __restrict__ parts, int n, doubl
 // ---- forward-only variant: the BCE sum of S, nothing else (validation in in-batch mode) ------------
 // inbatch_x_kernel's user role cut down to product 1 and the BCE terms: a block owns 32 kIblWaves
 // user rows and one split of the columns; a wave keeps its 32 rows' split-bf16 fragments in
-// registers, the positives stream through LDS in 64-row tiles of the same three-plane image
-// (ibx_off, ibx_split) and each 32 x 32 score block is formed by the same five partial products
-// (ibx_mfma6).  Every in-range element then adds its BCE term with the training kernel's
-// arithmetic (one hardware exp2 of -|x|, hardware log2; max(x, 0) + ln(1 + t) on label-free
-// interior blocks), so a batch's training and validation BCE are the same function of the same
-// rows.  No dS, no second product, no transposed LDS reads, no slabs: a block writes one float.
+// registers (ibx_row_frags), the positives stream through LDS in 64-row tiles of the same
+// three-plane image (IbxStage) and each 32 x 32 score block is formed by the same five partial
+// products (ibx_score).  Every in-range element then adds its BCE term with the training kernel's
+// arithmetic (ibx_exp_nabs, ibx_bce_free on label-free interior blocks, ibx_bce_term elsewhere), so
+// a batch's training and validation BCE are the same function of the same rows.  No dS, no second
+// product, no transposed LDS reads, no slabs: a block writes one float.
 // Without the dU accumulators and the second product's operands a wave needs fewer than 256
 // registers at every D, so a block is 8 waves (two per SIMD: one wave's elementwise pass runs under
 // the other's MFMAs), alone on its CU with the tile double buffered (96 KB LDS, one barrier per
@@ -945,9 +660,6 @@ __global__ __launch_bounds__(64 * kIblWaves, 1) void inbatch_loss_kernel(InBatch
     constexpr bool SOFTMAX = LOSS == TTAMM_INBATCH_SOFTMAX;
     constexpr int NT = 64 * kIblWaves;
     constexpr int KS = DP / 16;            // k steps of the score product
-    constexpr int TF4 = kIbTile * DP / 4;  // float4 per column tile
-    constexpr int LOADS = TF4 / NT;
-    static_assert(TF4 % NT == 0, "whole staging rounds");
     __shared__ __attribute__((aligned(16))) unsigned char tiles[2][3 * kIbxPlane];
     __shared__ float red[kIblWaves];
 
@@ -962,57 +674,17 @@ __global__ __launch_bounds__(64 * kIblWaves, 1) void inbatch_loss_kernel(InBatch
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, li = lane & 31, h = lane >> 5;
     const int64_t r0 = (int64_t)rb * kIblRows + 32 * w;
 
-    // this lane's row fragments (B operand): R[r0 + li][16 s + 8 h + j], zero past D / nr
     bf16x8_t rf[KS][3];
-    {
-        const int64_t row = r0 + li;
-        const bool rok = row < nr;
-#pragma unroll
-        for (int s = 0; s < KS; ++s) {
-            const int col = 16 * s + 8 * h;
-            const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
-            const float4 a = (rok && col < D) ? *reinterpret_cast<const float4*>(R + row * ldr + col) : z;
-            const float4 b = (rok && col + 4 < D) ? *reinterpret_cast<const float4*>(R + row * ldr + col + 4) : z;
-            uint2 pa[3], pb[3];
-            ibx_split(a, pa);
-            ibx_split(b, pb);
-#pragma unroll
-            for (int q = 0; q < 3; ++q) rf[s][q] = ibx_cat(pa[q], pb[q]);
-        }
-    }
+    ibx_row_frags(R + (r0 + li) * ldr, r0 + li < nr, D, h, rf);
     float bce = 0.f, bce_lin = 0.f, bce_log2 = 0.f;
     float m_run = kIbNegBig, s_run = 0.f, z_pos = kIbNegBig;  // softmax: this lane's columns of its row
 
-    // column tile -> registers (zero past c_end / D) -> the three planes of an LDS image
-    float4 st[LOADS];
-    auto load = [&](int64_t c0) {
-#pragma unroll
-        for (int it = 0; it < LOADS; ++it) {
-            const int lin = tid + it * NT;
-            const int row = lin / (DP / 4), col = (lin - row * (DP / 4)) * 4;
-            const int64_t gc = c0 + row;
-            st[it] = (gc < c_end && col < D) ? *reinterpret_cast<const float4*>(C + gc * ldc + col)
-                                             : make_float4(0.f, 0.f, 0.f, 0.f);
-        }
-    };
-    auto store = [&](unsigned char* dst) {
-#pragma unroll
-        for (int it = 0; it < LOADS; ++it) {
-            const int lin = tid + it * NT;
-            const int row = lin / (DP / 4), c4 = lin - row * (DP / 4);
-            const int o = ibx_off(row, c4 >> 1) + 8 * (c4 & 1);
-            uint2 pl[3];
-            ibx_split(st[it], pl);
-#pragma unroll
-            for (int q = 0; q < 3; ++q) *reinterpret_cast<uint2*>(dst + q * kIbxPlane + o) = pl[q];
-        }
-    };
-
+    IbxStage<DP, NT> stage{C, ldc, c_end, D, tid};
     const int ntiles = c_end > c_begin ? (int)((c_end - c_begin + kIbTile - 1) / kIbTile) : 0;
     if (ntiles > 0) {  // tile 0 in buffer 0, tile 1 in flight in registers
-        load(c_begin);
-        store(tiles[0]);
-        if (ntiles > 1) load(c_begin + kIbTile);
+        stage.load(c_begin);
+        stage.store(tiles[0]);
+        if (ntiles > 1) stage.load(c_begin + kIbTile);
     }
     __syncthreads();
     const int64_t gr = r0 + li;
@@ -1028,18 +700,8 @@ __global__ __launch_bounds__(64 * kIblWaves, 1) void inbatch_loss_kernel(InBatch
         const bool fast = cols_here == kIbTile && __builtin_amdgcn_ballot_w64(diag >= 0 || !row_ok) == 0;
 #pragma unroll
         for (int jc = 0; jc < 2; ++jc) {  // tile rows 32 jc .. 32 jc + 31
-            // S^T block [32 c x 32 u]: lane = user row r0 + li, register r = tile column
-            f32x16 s2;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) s2[r] = 0.f;
-#pragma unroll
-            for (int s = 0; s < KS; ++s) {
-                const int o = ibx_off(32 * jc + li, 2 * s + h);
-                bf16x8_t a[3];
-#pragma unroll
-                for (int q = 0; q < 3; ++q) a[q] = *reinterpret_cast<const bf16x8_t*>(tile + q * kIbxPlane + o);
-                s2 = ibx_mfma6<SOFTMAX ? TTAMM_IB_SOFTMAX_PRODUCTS : TTAMM_IB_PRODUCTS>(a, rf[s], s2);
-            }
+            // lane = user row r0 + li, register r = tile column
+            const f32x16 s2 = ibx_score<kIbxProducts<LOSS>>(tile, jc, li, h, rf);
             if constexpr (SOFTMAX) {
                 // online log-sum-exp of these 16 columns: z_scale > 0, so max z = z_scale max x
                 const float zc = A.z_scale;
@@ -1071,14 +733,10 @@ __global__ __launch_bounds__(64 * kIblWaves, 1) void inbatch_loss_kernel(InBatch
                 s_run = s_run * __builtin_amdgcn_exp2f(m_run - m_new) + add;
                 m_run = m_new;
             } else if (fast) {
-                // y = 0 everywhere: the term is max(x, 0) + ln(1 + t), t = exp(-|x|), summed as two
-                // lane sums (the log2 terms scaled by ln 2 once at the end)
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
                     const float x = s2[r];
-                    const float tx = __builtin_amdgcn_exp2f(-fabsf(x) * 1.4426950408889634f);
-                    bce_lin += fmaxf(x, 0.f);
-                    bce_log2 += __builtin_amdgcn_logf(1.0f + tx);
+                    ibx_bce_free(x, ibx_exp_nabs(x), bce_lin, bce_log2);
                 }
             } else {
 #pragma unroll
@@ -1087,16 +745,16 @@ __global__ __launch_bounds__(64 * kIblWaves, 1) void inbatch_loss_kernel(InBatch
                     const bool ok = row_ok && lc < cols_here;
                     const float y = lc == diag ? 1.0f : 0.0f;
                     const float x = s2[r];
-                    const float tx = __builtin_amdgcn_exp2f(-fabsf(x) * 1.4426950408889634f);
-                    if (ok) bce += (1.0f - y) * x + fmaxf(-x, 0.f) + __builtin_amdgcn_logf(1.0f + tx) * 0.6931471805599453f;
+                    const float tx = ibx_exp_nabs(x);
+                    if (ok) bce += ibx_bce_term(x, y, tx);
                 }
             }
         }
         // tile t + 1 (landed in registers during this tile's MFMAs) into the other buffer, last
         // read in tile t - 1 before that tile's barrier; tile t + 2 in flight
         if (t + 1 < ntiles) {
-            store(tiles[(t + 1) & 1]);
-            if (t + 2 < ntiles) load(c0 + 2 * kIbTile);
+            stage.store(tiles[(t + 1) & 1]);
+            if (t + 2 < ntiles) stage.load(c0 + 2 * kIbTile);
         }
         __syncthreads();
     }
@@ -1160,33 +818,27 @@ __global__ __launch_bounds__(256) void ib_lse_merge_kernel(InBatchLossArgs A) {
     if (threadIdx.x == 0) A.loss_part[blockIdx.x] = red[0];
 }
 
-}  // namespace
-
-// Waves per block of the split-bf16 kernel: 4 (128 rows per block, two blocks per CU, one tile
-// buffer), or TTAMM_IB_WAVES=8 (256 rows, one block per CU, double-buffered: the column tile staged
-// once for twice the rows, but the tile prefetch registers push D = 128 into spills — 9.3 vs
-// 3.15 ms at the C4 rank shape, profiles/r04_inbatch_variants.txt); the fp32-MFMA kernel
-// (TTAMM_FP32_MFMA=exact) always uses 4.
-int inbatch_waves() {
-    const char* mf = product_env("TTAMM_FP32_MFMA");
-    if (mf && std::strcmp(mf, "exact") == 0) return 4;
-    const char* env = dev_env("TTAMM_IB_WAVES");
-    return (env && std::atoi(env) == 8) ? 8 : 4;
+// ---- host: plans, the one problem check, the one D dispatch ------------------------------------------
+// f(std::integral_constant<int, DP>) for the kernels' D class DP = D rounded up to 32, 64, 96 or 128
+template <class F>
+void ib_dispatch_dp(int D, F&& f) {
+    switch ((D + 31) / 32 * 32) {
+        case 32: f(std::integral_constant<int, 32>{}); break;
+        case 64: f(std::integral_constant<int, 64>{}); break;
+        case 96: f(std::integral_constant<int, 96>{}); break;
+        default: f(std::integral_constant<int, 128>{}); break;
+    }
 }
 
-// TTAMM_IB_KERNEL=p: the software-pipelined one-wave-per-SIMD kernel (inbatch_p_kernel), one
-// launch per role
-bool inbatch_pipelined() {
-    const char* mf = product_env("TTAMM_FP32_MFMA");
-    if (mf && std::strcmp(mf, "exact") == 0) return false;
-    const char* env = dev_env("TTAMM_IB_KERNEL");
-    return env && std::strcmp(env, "p") == 0;
+bool ib_exact_mfma() {  // TTAMM_FP32_MFMA=exact: the v_mfma_f32_32x32x2_f32 kernel (as gemm.hip's switch)
+    const char* env = product_env("TTAMM_FP32_MFMA");
+    return env && std::strcmp(env, "exact") == 0;
 }
 
+// The gradient kernels' blocks: row blocks of kIbRows x column splits of whole tiles per role.
 void inbatch_plan(int64_t B, int64_t Bc, InBatchArgs& a) {
-    const int rows = inbatch_pipelined() ? kIbRows : 32 * inbatch_waves();
-    a.rblk_u = (int)ceil_div(B, rows);
-    a.rblk_p = (int)ceil_div(Bc, rows);
+    a.rblk_u = (int)ceil_div(B, kIbRows);
+    a.rblk_p = (int)ceil_div(Bc, kIbRows);
     // ~256 blocks per role (one resident round over both roles at two blocks per CU, each block
     // twice the columns of the former 512: C4 0.952 -> 0.924 ms/step, C2 in-batch 0.658 -> 0.625,
     // the C4 rank-of-8 shape unchanged, profiles/r04_s43_inbatch_blocks.txt); developer knob
@@ -1206,6 +858,68 @@ void inbatch_plan(int64_t B, int64_t Bc, InBatchArgs& a) {
     a.splits_p = (int)std::max<int64_t>(1, ceil_div(B, a.cols_p));
 }
 
+// The forward-only kernel's blocks: row blocks of kIblRows users x column splits of whole 64-column
+// tiles, ~kIblBlocks blocks: one 8-wave block per CU in a single resident round (the kernel's 96 KB
+// of LDS and two waves per SIMD allow one).  A function of the shapes only: no environment
+// variable moves the split.
+void inbatch_loss_plan(int64_t B, int64_t Bc, InBatchLossArgs& a) {
+    a.rblk = (int)ceil_div(B, kIblRows);
+    const int64_t want = std::min<int64_t>(ceil_div(Bc, kIbTile), ceil_div(kIblBlocks, a.rblk));
+    a.cols = ceil_div(ceil_div(Bc, std::max<int64_t>(1, want)), kIbTile) * kIbTile;
+    a.splits = (int)std::max<int64_t>(1, ceil_div(Bc, a.cols));
+}
+
+// What every kernel here needs of its rows; labels_inside: each user's own positive is a column
+// (the forward-only passes, which exclude nothing and look the label's logit up).
+int inbatch_problem_check(const InBatchProblem& p, bool labels_inside) {
+    int rc;
+    if ((rc = inbatch_loss_check(p.D))) return rc;
+    TTAMM_REQUIRE(p.B > 0 && p.Bc > 0 && p.B < (int64_t(1) << 31) && p.Bc < (int64_t(1) << 31), "in-batch: bad batch");
+    TTAMM_REQUIRE(p.ldu % 4 == 0 && p.ldp % 4 == 0 && ((uintptr_t)p.U | (uintptr_t)p.P) % 16 == 0,
+                  "in-batch: rows must be 16-byte aligned");
+    TTAMM_REQUIRE(!labels_inside || (p.row_base >= 0 && p.row_base + p.B <= p.Bc),
+                  "in-batch: the users' labels must lie inside the columns");
+    return TTAMM_OK;
+}
+
+// plan, one two-role launch of the gradient kernel (fp32 MFMA, or split-bf16 in its LOSS form), then
+// dU / dP = the slabs summed in split order
+int launch_inbatch_grad(InBatchArgs& a, int loss, bool exact, hipStream_t s) {
+    inbatch_plan(a.B, a.Bc, a);
+    const dim3 g((unsigned)(a.rblk_u * a.splits_u + a.rblk_p * a.splits_p)), t(2 * kIbRows);
+    ib_dispatch_dp(a.D, [&](auto dp) {
+        constexpr int DP = decltype(dp)::value;
+        if (exact) hipLaunchKernelGGL(inbatch_kernel<DP>, g, t, 0, s, a);
+        // D = 128 at two blocks per CU spills ~20 registers and still beats one block per CU
+        // (C4: 0.41 vs 0.50 ms per launch)
+        else if (loss == TTAMM_INBATCH_SOFTMAX) hipLaunchKernelGGL((inbatch_x_kernel<DP, TTAMM_INBATCH_SOFTMAX>), g, t, 0, s, a);
+        else hipLaunchKernelGGL((inbatch_x_kernel<DP, TTAMM_INBATCH_BCE>), g, t, 0, s, a);
+    });
+    TTAMM_LAUNCH_CHECK();
+    const int64_t total = (a.B + a.Bc) * a.D;
+    hipLaunchKernelGGL(ib_reduce_kernel, dim3((unsigned)std::min<int64_t>(ceil_div(total, 256), 8192)), dim3(256), 0, s,
+                       a);
+    TTAMM_LAUNCH_CHECK();
+    return TTAMM_OK;
+}
+
+// check, plan, one launch of the forward-only kernel in its LOSS form
+int launch_inbatch_scores(InBatchLossArgs& a, int loss, hipStream_t s) {
+    int rc;
+    if ((rc = inbatch_problem_check(a, true))) return rc;
+    inbatch_loss_plan(a.B, a.Bc, a);
+    const dim3 g((unsigned)(a.rblk * a.splits)), t(64 * kIblWaves);
+    ib_dispatch_dp(a.D, [&](auto dp) {
+        constexpr int DP = decltype(dp)::value;
+        if (loss == TTAMM_INBATCH_SOFTMAX) hipLaunchKernelGGL((inbatch_loss_kernel<DP, TTAMM_INBATCH_SOFTMAX>), g, t, 0, s, a);
+        else hipLaunchKernelGGL((inbatch_loss_kernel<DP, TTAMM_INBATCH_BCE>), g, t, 0, s, a);
+    });
+    TTAMM_LAUNCH_CHECK();
+    return TTAMM_OK;
+}
+
+}  // namespace
+
 size_t inbatch_workspace_floats(int64_t B, int64_t Bc, int D, size_t* slab_u, size_t* slab_p, size_t* parts) {
     InBatchArgs a{};
     inbatch_plan(B, Bc, a);
@@ -1215,157 +929,31 @@ size_t inbatch_workspace_floats(int64_t B, int64_t Bc, int D, size_t* slab_u, si
     return *slab_u + *slab_p + *parts;
 }
 
-static int inbatch_check(const InBatchArgs& a) {
-    TTAMM_REQUIRE(a.D > 0 && a.D % 4 == 0 && a.D <= 128, "in-batch negatives: embedding dim must be a multiple of 4, <= 128");
-    TTAMM_REQUIRE(a.B > 0 && a.Bc > 0 && a.B < (int64_t(1) << 31) && a.Bc < (int64_t(1) << 31), "in-batch: bad batch");
-    TTAMM_REQUIRE(a.ldu % 4 == 0 && a.ldp % 4 == 0 && ((uintptr_t)a.U | (uintptr_t)a.P) % 16 == 0,
-                  "in-batch: rows must be 16-byte aligned");
+int inbatch_loss_check(int D) {
+    TTAMM_REQUIRE(D > 0 && D % 4 == 0 && D <= 128, "in-batch negatives: embedding dim must be a multiple of 4, <= 128");
     return TTAMM_OK;
 }
 
-// dU / dP = the slabs summed in split order
-static int launch_inbatch_reduce(const InBatchArgs& a, hipStream_t s) {
-    const int64_t total = (a.B + a.Bc) * a.D;
-    hipLaunchKernelGGL(ib_reduce_kernel, dim3((unsigned)std::min<int64_t>(ceil_div(total, 256), 8192)), dim3(256), 0, s,
-                       a);
-    TTAMM_LAUNCH_CHECK();
+int inbatch_softmax_check(float inv_temperature) {
+    TTAMM_REQUIRE(std::isfinite(inv_temperature) && inv_temperature > 0.f,
+                  "in-batch softmax: the inverse temperature must be finite and greater than zero");
     return TTAMM_OK;
 }
 
 int launch_inbatch(InBatchArgs& a, hipStream_t s) {
     int rc;
-    if ((rc = inbatch_check(a))) return rc;
-    inbatch_plan(a.B, a.Bc, a);
-    const unsigned blocks = (unsigned)(a.rblk_u * a.splits_u + a.rblk_p * a.splits_p);
-    const int dp = (a.D + 31) / 32 * 32;
-    // TTAMM_FP32_MFMA=exact: the v_mfma_f32_32x32x2_f32 kernel (as gemm.hip's developer switch)
-    const char* env = product_env("TTAMM_FP32_MFMA");
-    if (env && std::strcmp(env, "exact") == 0) {
-        switch (dp) {
-            case 32: hipLaunchKernelGGL(inbatch_kernel<32>, dim3(blocks), dim3(256), 0, s, a); break;
-            case 64: hipLaunchKernelGGL(inbatch_kernel<64>, dim3(blocks), dim3(256), 0, s, a); break;
-            case 96: hipLaunchKernelGGL(inbatch_kernel<96>, dim3(blocks), dim3(256), 0, s, a); break;
-            default: hipLaunchKernelGGL(inbatch_kernel<128>, dim3(blocks), dim3(256), 0, s, a); break;
-        }
-    } else {
-        if (inbatch_pipelined()) {
-            const unsigned bu = (unsigned)(a.rblk_u * a.splits_u), bp = (unsigned)(a.rblk_p * a.splits_p);
-            switch (dp) {
-                case 32:
-                    hipLaunchKernelGGL((inbatch_p_kernel<32, true>), dim3(bu), dim3(256), 0, s, a);
-                    hipLaunchKernelGGL((inbatch_p_kernel<32, false>), dim3(bp), dim3(256), 0, s, a);
-                    break;
-                case 64:
-                    hipLaunchKernelGGL((inbatch_p_kernel<64, true>), dim3(bu), dim3(256), 0, s, a);
-                    hipLaunchKernelGGL((inbatch_p_kernel<64, false>), dim3(bp), dim3(256), 0, s, a);
-                    break;
-                case 96:
-                    hipLaunchKernelGGL((inbatch_p_kernel<96, true>), dim3(bu), dim3(256), 0, s, a);
-                    hipLaunchKernelGGL((inbatch_p_kernel<96, false>), dim3(bp), dim3(256), 0, s, a);
-                    break;
-                default:
-                    hipLaunchKernelGGL((inbatch_p_kernel<128, true>), dim3(bu), dim3(256), 0, s, a);
-                    hipLaunchKernelGGL((inbatch_p_kernel<128, false>), dim3(bp), dim3(256), 0, s, a);
-                    break;
-            }
-        } else if (inbatch_waves() == 8) {
-            switch (dp) {
-                case 32: hipLaunchKernelGGL((inbatch_x_kernel<32, 1, 8, true>), dim3(blocks), dim3(512), 0, s, a); break;
-                case 64: hipLaunchKernelGGL((inbatch_x_kernel<64, 1, 8, true>), dim3(blocks), dim3(512), 0, s, a); break;
-                case 96: hipLaunchKernelGGL((inbatch_x_kernel<96, 1, 8, true>), dim3(blocks), dim3(512), 0, s, a); break;
-                default: hipLaunchKernelGGL((inbatch_x_kernel<128, 1, 8, true>), dim3(blocks), dim3(512), 0, s, a); break;
-            }
-        } else {
-            switch (dp) {
-                case 32: hipLaunchKernelGGL((inbatch_x_kernel<32, 2, 4, false>), dim3(blocks), dim3(256), 0, s, a); break;
-                case 64: hipLaunchKernelGGL((inbatch_x_kernel<64, 2, 4, false>), dim3(blocks), dim3(256), 0, s, a); break;
-                case 96: hipLaunchKernelGGL((inbatch_x_kernel<96, 2, 4, false>), dim3(blocks), dim3(256), 0, s, a); break;
-                // D = 128 at two blocks per CU spills ~20 registers and still beats one block per CU
-                // (C4: 0.41 vs 0.50 ms per launch)
-                default: hipLaunchKernelGGL((inbatch_x_kernel<128, 2, 4, false>), dim3(blocks), dim3(256), 0, s, a); break;
-            }
-        }
-    }
-    TTAMM_LAUNCH_CHECK();
-    return launch_inbatch_reduce(a, s);
-}
-
-size_t inbatch_standalone_workspace_bytes(int64_t B, int64_t Bc, int D) {
-    size_t su, sp, parts;
-    inbatch_workspace_floats(B, Bc, D, &su, &sp, &parts);
-    return sizeof(float) * (su + sp + parts);
-}
-
-int inbatch_standalone(const float* U, int64_t B, int64_t ldu, const float* P, int64_t Bc, int64_t ldp, int D,
-                       int64_t row_base, float inv_T, float* dU, int64_t ld_du, float* dP, int64_t ld_dp,
-                       double* loss_sum, void* ws, size_t ws_bytes, hipStream_t s) {
-    TTAMM_REQUIRE(U && P && dU && dP && loss_sum && ws, "inbatch_bce: null argument");
-    TTAMM_REQUIRE(B > 0 && Bc > 0 && D > 0 && ldu >= D && ldp >= D && ld_du >= D && ld_dp >= D,
-                  "inbatch_bce: bad shape");
-    TTAMM_REQUIRE(row_base >= 0 && row_base + B <= Bc,
-                  "inbatch_bce: row_base must place the B users' labels inside the Bc columns (0 <= row_base, "
-                  "row_base + B <= Bc)");
-    TTAMM_REQUIRE(ws_bytes >= inbatch_standalone_workspace_bytes(B, Bc, D), "inbatch_bce: workspace too small");
-    InBatchArgs a{};
-    a.U = U, a.ldu = ldu, a.B = B, a.P = P, a.ldp = ldp, a.Bc = Bc, a.D = D;
-    a.row_base = row_base, a.inv_T = inv_T;
-    size_t su, sp, parts;
-    inbatch_workspace_floats(B, Bc, D, &su, &sp, &parts);
-    float* w = static_cast<float*>(ws);
-    a.slab_u = w, a.slab_p = w + su, a.loss_part = w + su + sp;
-    a.dU = dU, a.ld_du = ld_du, a.dP = dP, a.ld_dp = ld_dp;
-    const int rc = launch_inbatch(a, s);
-    if (rc != TTAMM_OK) return rc;
-    hipLaunchKernelGGL(ib_loss_sum_kernel, dim3(1), dim3(256), 0, s, a.loss_part, a.rblk_u * a.splits_u, loss_sum);
-    TTAMM_LAUNCH_CHECK();
-    return TTAMM_OK;
+    if ((rc = inbatch_problem_check(a, false))) return rc;
+    return launch_inbatch_grad(a, TTAMM_INBATCH_BCE, ib_exact_mfma(), s);
 }
 
 // ---- forward-only BCE sum (inbatch_loss_kernel) ----------------------------------------------------
-// Row blocks of kIblRows users x column splits of whole 64-column tiles, ~kIblBlocks blocks: one
-// 8-wave block per CU in a single resident round (the kernel's 96 KB of LDS and two waves per SIMD
-// allow one).  A function of the shapes only: no environment variable moves the split.
-void inbatch_loss_plan(int64_t B, int64_t Bc, InBatchLossArgs& a) {
-    a.rblk = (int)ceil_div(B, kIblRows);
-    const int64_t want = std::min<int64_t>(ceil_div(Bc, kIbTile), ceil_div(kIblBlocks, a.rblk));
-    a.cols = ceil_div(ceil_div(Bc, std::max<int64_t>(1, want)), kIbTile) * kIbTile;
-    a.splits = (int)std::max<int64_t>(1, ceil_div(Bc, a.cols));
-}
-
 int inbatch_loss_blocks(int64_t B, int64_t Bc) {
     InBatchLossArgs a{};
     inbatch_loss_plan(B, Bc, a);
     return a.rblk * a.splits;
 }
 
-int inbatch_loss_check(int D) {
-    TTAMM_REQUIRE(D > 0 && D % 4 == 0 && D <= 128, "in-batch negatives: embedding dim must be a multiple of 4, <= 128");
-    return TTAMM_OK;
-}
-
-int launch_inbatch_loss(InBatchLossArgs& a, hipStream_t s) {
-    int rc;
-    if ((rc = inbatch_loss_check(a.D))) return rc;
-    TTAMM_REQUIRE(a.B > 0 && a.Bc > 0 && a.B < (int64_t(1) << 31) && a.Bc < (int64_t(1) << 31), "in-batch: bad batch");
-    TTAMM_REQUIRE(a.ldu % 4 == 0 && a.ldp % 4 == 0 && ((uintptr_t)a.U | (uintptr_t)a.P) % 16 == 0,
-                  "in-batch: rows must be 16-byte aligned");
-    TTAMM_REQUIRE(a.row_base >= 0 && a.row_base + a.B <= a.Bc, "in-batch: the users' labels must lie inside the columns");
-    inbatch_loss_plan(a.B, a.Bc, a);
-    const dim3 g((unsigned)(a.rblk * a.splits)), t(64 * kIblWaves);
-    switch ((a.D + 31) / 32 * 32) {
-        case 32: hipLaunchKernelGGL(inbatch_loss_kernel<32>, g, t, 0, s, a); break;
-        case 64: hipLaunchKernelGGL(inbatch_loss_kernel<64>, g, t, 0, s, a); break;
-        case 96: hipLaunchKernelGGL(inbatch_loss_kernel<96>, g, t, 0, s, a); break;
-        default: hipLaunchKernelGGL(inbatch_loss_kernel<128>, g, t, 0, s, a); break;
-    }
-    TTAMM_LAUNCH_CHECK();
-    return TTAMM_OK;
-}
-
-size_t inbatch_loss_workspace_bytes(int64_t B, int64_t Bc, int D) {
-    (void)D;
-    return sizeof(float) * (size_t)inbatch_loss_blocks(B, Bc);
-}
+int launch_inbatch_loss(InBatchLossArgs& a, hipStream_t s) { return launch_inbatch_scores(a, TTAMM_INBATCH_BCE, s); }
 
 // ---- in-batch softmax: the LSE pass, then inbatch_x_kernel's softmax instantiation -----------------
 // The LSE pass runs on inbatch_loss_plan's blocks (a function of the shapes only); its workspace is
@@ -1389,32 +977,13 @@ void inbatch_lse_bind(InBatchLossArgs& a, float* w) {
     a.loss_part = a.rinv + a.B;
 }
 
-int inbatch_softmax_check(float inv_temperature) {
-    TTAMM_REQUIRE(std::isfinite(inv_temperature) && inv_temperature > 0.f,
-                  "in-batch softmax: the inverse temperature must be finite and greater than zero");
-    return TTAMM_OK;
-}
-
 int launch_inbatch_lse(InBatchLossArgs& a, float inv_temperature, hipStream_t s) {
     int rc;
-    if ((rc = inbatch_loss_check(a.D))) return rc;
     if ((rc = inbatch_softmax_check(inv_temperature))) return rc;
-    TTAMM_REQUIRE(a.B > 0 && a.Bc > 0 && a.B < (int64_t(1) << 31) && a.Bc < (int64_t(1) << 31), "in-batch: bad batch");
-    TTAMM_REQUIRE(a.ldu % 4 == 0 && a.ldp % 4 == 0 && ((uintptr_t)a.U | (uintptr_t)a.P) % 16 == 0,
-                  "in-batch: rows must be 16-byte aligned");
-    TTAMM_REQUIRE(a.row_base >= 0 && a.row_base + a.B <= a.Bc, "in-batch: the users' labels must lie inside the columns");
     TTAMM_REQUIRE(a.ms && a.zpos && a.lse && a.term && a.rmax && a.rinv && a.loss_part && (uintptr_t)a.ms % 8 == 0,
                   "in-batch softmax: LSE workspace not bound");
-    inbatch_loss_plan(a.B, a.Bc, a);
     a.z_scale = inv_temperature * 1.4426950408889634f;
-    const dim3 g((unsigned)(a.rblk * a.splits)), t(64 * kIblWaves);
-    switch ((a.D + 31) / 32 * 32) {
-        case 32: hipLaunchKernelGGL((inbatch_loss_kernel<32, TTAMM_INBATCH_SOFTMAX>), g, t, 0, s, a); break;
-        case 64: hipLaunchKernelGGL((inbatch_loss_kernel<64, TTAMM_INBATCH_SOFTMAX>), g, t, 0, s, a); break;
-        case 96: hipLaunchKernelGGL((inbatch_loss_kernel<96, TTAMM_INBATCH_SOFTMAX>), g, t, 0, s, a); break;
-        default: hipLaunchKernelGGL((inbatch_loss_kernel<128, TTAMM_INBATCH_SOFTMAX>), g, t, 0, s, a); break;
-    }
-    TTAMM_LAUNCH_CHECK();
+    if ((rc = launch_inbatch_scores(a, TTAMM_INBATCH_SOFTMAX, s))) return rc;
     hipLaunchKernelGGL(ib_lse_merge_kernel, dim3((unsigned)inbatch_lse_parts(a.B)), dim3(256), 0, s, a);
     TTAMM_LAUNCH_CHECK();
     return TTAMM_OK;
@@ -1422,113 +991,73 @@ int launch_inbatch_lse(InBatchLossArgs& a, float inv_temperature, hipStream_t s)
 
 int launch_inbatch_softmax(InBatchArgs& a, InBatchLossArgs& l, float inv_temperature, hipStream_t s) {
     int rc;
-    if ((rc = inbatch_check(a))) return rc;
+    if ((rc = inbatch_problem_check(a, false))) return rc;
     if ((rc = launch_inbatch_lse(l, inv_temperature, s))) return rc;
     a.rmax = l.rmax, a.rinv = l.rinv;
     a.z_scale = l.z_scale;
     a.inv_T *= inv_temperature;  // dS = (p - y) inv_count / temperature
-    inbatch_plan(a.B, a.Bc, a);
-    const unsigned blocks = (unsigned)(a.rblk_u * a.splits_u + a.rblk_p * a.splits_p);
-    constexpr int SM = TTAMM_INBATCH_SOFTMAX;
-    const int dp = (a.D + 31) / 32 * 32;
-    // the plan's rows per block: 256 with TTAMM_IB_WAVES=8, unless TTAMM_IB_KERNEL=p planned 128
-    if (!inbatch_pipelined() && inbatch_waves() == 8) {
-        switch (dp) {
-            case 32: hipLaunchKernelGGL((inbatch_x_kernel<32, 1, 8, true, SM>), dim3(blocks), dim3(512), 0, s, a); break;
-            case 64: hipLaunchKernelGGL((inbatch_x_kernel<64, 1, 8, true, SM>), dim3(blocks), dim3(512), 0, s, a); break;
-            case 96: hipLaunchKernelGGL((inbatch_x_kernel<96, 1, 8, true, SM>), dim3(blocks), dim3(512), 0, s, a); break;
-            default: hipLaunchKernelGGL((inbatch_x_kernel<128, 1, 8, true, SM>), dim3(blocks), dim3(512), 0, s, a); break;
-        }
-    } else {
-        switch (dp) {
-            case 32: hipLaunchKernelGGL((inbatch_x_kernel<32, 2, 4, false, SM>), dim3(blocks), dim3(256), 0, s, a); break;
-            case 64: hipLaunchKernelGGL((inbatch_x_kernel<64, 2, 4, false, SM>), dim3(blocks), dim3(256), 0, s, a); break;
-            case 96: hipLaunchKernelGGL((inbatch_x_kernel<96, 2, 4, false, SM>), dim3(blocks), dim3(256), 0, s, a); break;
-            default: hipLaunchKernelGGL((inbatch_x_kernel<128, 2, 4, false, SM>), dim3(blocks), dim3(256), 0, s, a); break;
-        }
-    }
-    TTAMM_LAUNCH_CHECK();
-    return launch_inbatch_reduce(a, s);
+    return launch_inbatch_grad(a, TTAMM_INBATCH_SOFTMAX, false, s);
 }
 
-size_t inbatch_softmax_workspace_bytes(int64_t B, int64_t Bc, int D) {
-    return sizeof(float) * inbatch_lse_floats(B, Bc) + inbatch_standalone_workspace_bytes(B, Bc, D);
-}
-
-size_t inbatch_softmax_loss_workspace_bytes(int64_t B, int64_t Bc, int D) {
-    (void)D;
-    return sizeof(float) * inbatch_lse_floats(B, Bc);
-}
-
-int inbatch_softmax_loss_standalone(const float* U, int64_t B, int64_t ldu, const float* P, int64_t Bc, int64_t ldp,
-                                    int D, int64_t row_base, float inv_temperature, double* loss_sum, void* ws,
-                                    size_t ws_bytes, hipStream_t s) {
-    int rc;
-    TTAMM_REQUIRE(U && P && loss_sum && ws, "inbatch_softmax_loss: null argument");
-    TTAMM_REQUIRE(B > 0 && Bc > 0 && D > 0 && ldu >= D && ldp >= D, "inbatch_softmax_loss: bad shape");
-    TTAMM_REQUIRE(row_base >= 0 && row_base + B <= Bc,
-                  "inbatch_softmax_loss: row_base must place the B users' labels inside the Bc columns (0 <= row_base, "
-                  "row_base + B <= Bc)");
-    if ((rc = inbatch_softmax_check(inv_temperature))) return rc;
-    if ((rc = inbatch_loss_check(D))) return rc;
-    TTAMM_REQUIRE(ws_bytes >= inbatch_softmax_loss_workspace_bytes(B, Bc, D), "inbatch_softmax_loss: workspace too small");
-    InBatchLossArgs l{};
-    l.U = U, l.ldu = ldu, l.B = B, l.P = P, l.ldp = ldp, l.Bc = Bc, l.D = D;
-    l.row_base = row_base;
-    inbatch_lse_bind(l, static_cast<float*>(ws));
-    if ((rc = launch_inbatch_lse(l, inv_temperature, s))) return rc;
-    hipLaunchKernelGGL(ib_loss_sum_kernel, dim3(1), dim3(256), 0, s, l.loss_part, inbatch_lse_parts(B), loss_sum);
-    TTAMM_LAUNCH_CHECK();
-    return TTAMM_OK;
-}
-
-int inbatch_softmax_standalone(const float* U, int64_t B, int64_t ldu, const float* P, int64_t Bc, int64_t ldp, int D,
-                               int64_t row_base, float inv_count, float inv_temperature, float* dU, int64_t ld_du,
-                               float* dP, int64_t ld_dp, double* loss_sum, void* ws, size_t ws_bytes, hipStream_t s) {
-    int rc;
-    TTAMM_REQUIRE(U && P && dU && dP && loss_sum && ws, "inbatch_softmax: null argument");
-    TTAMM_REQUIRE(B > 0 && Bc > 0 && D > 0 && ldu >= D && ldp >= D && ld_du >= D && ld_dp >= D,
-                  "inbatch_softmax: bad shape");
-    TTAMM_REQUIRE(row_base >= 0 && row_base + B <= Bc,
-                  "inbatch_softmax: row_base must place the B users' labels inside the Bc columns (0 <= row_base, "
-                  "row_base + B <= Bc)");
-    if ((rc = inbatch_softmax_check(inv_temperature))) return rc;
-    if ((rc = inbatch_loss_check(D))) return rc;
-    TTAMM_REQUIRE(ws_bytes >= inbatch_softmax_workspace_bytes(B, Bc, D), "inbatch_softmax: workspace too small");
-    InBatchLossArgs l{};
-    l.U = U, l.ldu = ldu, l.B = B, l.P = P, l.ldp = ldp, l.Bc = Bc, l.D = D;
-    l.row_base = row_base;
-    float* w = static_cast<float*>(ws);
-    inbatch_lse_bind(l, w);
-    w += inbatch_lse_floats(B, Bc);
-    InBatchArgs a{};
-    a.U = U, a.ldu = ldu, a.B = B, a.P = P, a.ldp = ldp, a.Bc = Bc, a.D = D;
-    a.row_base = row_base, a.inv_T = inv_count;
+// ---- the four one-call ops (ttamm_inbatch_bce, _bce_loss, _softmax, _softmax_loss) -------------------
+// An op's workspace: [the LSE block (softmax) | slab_u | slab_p | loss_part (with gradients)], or the
+// forward-only BCE kernel's block sums alone.
+size_t inbatch_op_workspace_bytes(int loss, bool grads, int64_t B, int64_t Bc, int D) {
     size_t su, sp, parts;
-    inbatch_workspace_floats(B, Bc, D, &su, &sp, &parts);
-    a.slab_u = w, a.slab_p = w + su, a.loss_part = w + su + sp;
-    a.dU = dU, a.ld_du = ld_du, a.dP = dP, a.ld_dp = ld_dp;
-    if ((rc = launch_inbatch_softmax(a, l, inv_temperature, s))) return rc;
-    hipLaunchKernelGGL(ib_loss_sum_kernel, dim3(1), dim3(256), 0, s, l.loss_part, inbatch_lse_parts(B), loss_sum);
-    TTAMM_LAUNCH_CHECK();
-    return TTAMM_OK;
+    const size_t lse = loss == TTAMM_INBATCH_SOFTMAX ? inbatch_lse_floats(B, Bc) : 0;
+    if (grads) return sizeof(float) * (lse + inbatch_workspace_floats(B, Bc, D, &su, &sp, &parts));
+    return sizeof(float) * (lse ? lse : (size_t)inbatch_loss_blocks(B, Bc));
 }
 
-int inbatch_loss_standalone(const float* U, int64_t B, int64_t ldu, const float* P, int64_t Bc, int64_t ldp, int D,
-                            int64_t row_base, double* loss_sum, void* ws, size_t ws_bytes, hipStream_t s) {
-    TTAMM_REQUIRE(U && P && loss_sum && ws, "inbatch_bce_loss: null argument");
-    TTAMM_REQUIRE(B > 0 && Bc > 0 && D > 0 && ldu >= D && ldp >= D, "inbatch_bce_loss: bad shape");
-    TTAMM_REQUIRE(row_base >= 0 && row_base + B <= Bc,
-                  "inbatch_bce_loss: row_base must place the B users' labels inside the Bc columns (0 <= row_base, "
-                  "row_base + B <= Bc)");
-    TTAMM_REQUIRE(ws_bytes >= inbatch_loss_workspace_bytes(B, Bc, D), "inbatch_bce_loss: workspace too small");
-    InBatchLossArgs a{};
-    a.U = U, a.ldu = ldu, a.B = B, a.P = P, a.ldp = ldp, a.Bc = Bc, a.D = D;
-    a.row_base = row_base;
-    a.loss_part = static_cast<float*>(ws);
-    const int rc = launch_inbatch_loss(a, s);
+int inbatch_op(int loss, bool grads, const InBatchProblem& p, float inv_count, float inv_temperature, float* dU,
+               int64_t ld_du, float* dP, int64_t ld_dp, double* loss_sum, void* ws, size_t ws_bytes, hipStream_t s) {
+    const bool softmax = loss == TTAMM_INBATCH_SOFTMAX;
+    const std::string op = std::string(softmax ? "inbatch_softmax" : "inbatch_bce") + (grads ? "" : "_loss");
+    int rc;
+    TTAMM_REQUIRE(p.U && p.P && loss_sum && ws && (!grads || (dU && dP)), op + ": null argument");
+    TTAMM_REQUIRE(p.B > 0 && p.Bc > 0 && p.D > 0 && p.ldu >= p.D && p.ldp >= p.D &&
+                      (!grads || (ld_du >= p.D && ld_dp >= p.D)),
+                  op + ": bad shape");
+    TTAMM_REQUIRE(p.row_base >= 0 && p.row_base + p.B <= p.Bc,
+                  op + ": row_base must place the B users' labels inside the Bc columns (0 <= row_base, "
+                       "row_base + B <= Bc)");
+    if (softmax && (rc = inbatch_softmax_check(inv_temperature))) return rc;
+    if ((rc = inbatch_loss_check(p.D))) return rc;
+    TTAMM_REQUIRE(ws_bytes >= inbatch_op_workspace_bytes(loss, grads, p.B, p.Bc, p.D), op + ": workspace too small");
+    // bind: the forward pass's block, then the gradient pass's slabs
+    float* w = static_cast<float*>(ws);
+    InBatchLossArgs l{};
+    static_cast<InBatchProblem&>(l) = p;
+    if (softmax) {
+        inbatch_lse_bind(l, w);
+        w += inbatch_lse_floats(p.B, p.Bc);
+    } else {
+        l.loss_part = w;
+    }
+    InBatchArgs a{};
+    static_cast<InBatchProblem&>(a) = p;
+    if (grads) {
+        size_t su, sp, parts;
+        inbatch_workspace_floats(p.B, p.Bc, p.D, &su, &sp, &parts);
+        a.slab_u = w, a.slab_p = w + su, a.loss_part = w + su + sp;
+        a.inv_T = inv_count;
+        a.dU = dU, a.ld_du = ld_du, a.dP = dP, a.ld_dp = ld_dp;
+    }
+    // run: the loss's partial sums are the LSE merge's (softmax), the gradient kernel's user blocks'
+    // or the forward-only kernel's blocks'
+    const float* parts = l.loss_part;
+    int n = inbatch_lse_parts(p.B);
+    if (softmax) {
+        rc = grads ? launch_inbatch_softmax(a, l, inv_temperature, s) : launch_inbatch_lse(l, inv_temperature, s);
+    } else if (grads) {
+        rc = launch_inbatch(a, s);
+        parts = a.loss_part, n = a.rblk_u * a.splits_u;
+    } else {
+        rc = launch_inbatch_loss(l, s);
+        n = l.rblk * l.splits;
+    }
     if (rc != TTAMM_OK) return rc;
-    hipLaunchKernelGGL(ib_loss_sum_kernel, dim3(1), dim3(256), 0, s, a.loss_part, a.rblk * a.splits, loss_sum);
+    hipLaunchKernelGGL(ib_loss_sum_kernel, dim3(1), dim3(256), 0, s, parts, n, loss_sum);
     TTAMM_LAUNCH_CHECK();
     return TTAMM_OK;
 }

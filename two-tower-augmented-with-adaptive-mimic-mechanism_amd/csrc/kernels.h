@@ -382,13 +382,18 @@ int launch_loss_finalize(const float* partials, int blocks, const float* ib_part
 // ------------------------------------------------------------------------------------
 // In-batch negatives: S = U P^T with BCE, dU, dP (inbatch.hip)
 // ------------------------------------------------------------------------------------
-struct InBatchArgs {
+// The rows every in-batch pass works on: filled once by a caller, the base of both kernels'
+// arguments (so the kernel-argument layouts start with these fields in this order).
+struct InBatchProblem {
     const float* U;      // [B, ldu] augmented user rows (rows of S)
     int64_t ldu, B;
     const float* P;      // [Bc, ldp] augmented positive rows of the (global) batch (columns of S)
     int64_t ldp, Bc;
     int D;
     int64_t row_base;    // column of user 0's own positive (global batch position of the rank)
+};
+static_assert(sizeof(InBatchProblem) == 64, "no tail padding: the derived arguments follow at offset 64");
+struct InBatchArgs : InBatchProblem {
     float inv_T;         // 1 / logits in the BCE mean
     float* slab_u;       // [splits_u, B, D]
     float* slab_p;       // [splits_p, Bc, D]
@@ -405,22 +410,13 @@ struct InBatchArgs {
     const float* rinv;   // [B] 1 / the rows' sum of exp2(S * z_scale - rmax) (InBatchLossArgs.rinv)
     float z_scale;       // log2(e) / temperature
 };
-void inbatch_plan(int64_t B, int64_t Bc, InBatchArgs& a);
+// slab_u + slab_p + loss_part, in floats
 size_t inbatch_workspace_floats(int64_t B, int64_t Bc, int D, size_t* slab_u, size_t* slab_p, size_t* parts);
+// plans, launches the gradient kernel (TTAMM_FP32_MFMA=exact: the fp32-MFMA one) and the slab reduce
 int launch_inbatch(InBatchArgs& a, hipStream_t s);
-size_t inbatch_standalone_workspace_bytes(int64_t B, int64_t Bc, int D);
-int inbatch_standalone(const float* U, int64_t B, int64_t ldu, const float* P, int64_t Bc, int64_t ldp, int D,
-                       int64_t row_base, float inv_T, float* dU, int64_t ld_du, float* dP, int64_t ld_dp,
-                       double* loss_sum, void* ws, size_t ws_bytes, hipStream_t s);
 // Forward only: the BCE terms of S summed per block, no dS / dU / dP (inbatch_loss_kernel; the
 // validation pass in in-batch mode).  Always the split-bf16 products (TTAMM_FP32_MFMA is not read).
-struct InBatchLossArgs {
-    const float* U;      // [B, ldu] augmented user rows (rows of S)
-    int64_t ldu, B;
-    const float* P;      // [Bc, ldp] augmented positive rows (columns of S)
-    int64_t ldp, Bc;
-    int D;
-    int64_t row_base;    // column of user 0's own positive
+struct InBatchLossArgs : InBatchProblem {
     float* loss_part;    // [rblk * splits] BCE sums of the blocks
     // filled by inbatch_loss_plan
     int rblk, splits;
@@ -434,18 +430,14 @@ struct InBatchLossArgs {
     float* rmax;         // [B] the row's maximum logit in log2 units and
     float* rinv;         // [B] 1 / its sum of exp2(z - rmax): the gradient pass's normaliser
 };
-void inbatch_loss_plan(int64_t B, int64_t Bc, InBatchLossArgs& a);
 int inbatch_loss_blocks(int64_t B, int64_t Bc);  // floats of loss_part
-int inbatch_loss_check(int D);                   // the kernel's limits: D % 4 == 0, D <= 128
+int inbatch_loss_check(int D);                   // the kernels' limits: D % 4 == 0, D <= 128
 int launch_inbatch_loss(InBatchLossArgs& a, hipStream_t s);
-size_t inbatch_loss_workspace_bytes(int64_t B, int64_t Bc, int D);
-int inbatch_loss_standalone(const float* U, int64_t B, int64_t ldu, const float* P, int64_t Bc, int64_t ldp, int D,
-                            int64_t row_base, double* loss_sum, void* ws, size_t ws_bytes, hipStream_t s);
 // In-batch softmax cross-entropy over the rows of S / temperature (ttamm.h ttamm_inbatch_softmax).
 // Two passes: the LSE pass (inbatch_loss_kernel's softmax form, then ib_lse_merge_kernel) owns the
 // loss and the rows' normalisers; the gradient pass is inbatch_x_kernel's softmax instantiation, which
-// reads (rmax, rinv) and accumulates no loss.  Always the split-bf16 inbatch_x_kernel: TTAMM_FP32_MFMA=exact and
-// TTAMM_IB_KERNEL=p are not honoured under softmax (neither variant has a softmax form).
+// reads (rmax, rinv) and accumulates no loss.  Always the split-bf16 inbatch_x_kernel:
+// TTAMM_FP32_MFMA=exact is not honoured under softmax (the fp32-MFMA kernel has no softmax form).
 int inbatch_lse_parts(int64_t B);                     // floats of the merge kernel's loss_part
 size_t inbatch_lse_floats(int64_t B, int64_t Bc);     // ms + zpos + lse + term + rmax + rinv + loss_part
 void inbatch_lse_bind(InBatchLossArgs& a, float* w);  // a.B / a.Bc set; w holds inbatch_lse_floats
@@ -453,14 +445,13 @@ int inbatch_softmax_check(float inv_temperature);     // finite and > 0
 int launch_inbatch_lse(InBatchLossArgs& a, float inv_temperature, hipStream_t s);
 // a.rmax / a.rinv / a.z_scale are taken from the LSE pass l, which is launched first; a.inv_T = inv_count
 int launch_inbatch_softmax(InBatchArgs& a, InBatchLossArgs& l, float inv_temperature, hipStream_t s);
-size_t inbatch_softmax_workspace_bytes(int64_t B, int64_t Bc, int D);
-int inbatch_softmax_standalone(const float* U, int64_t B, int64_t ldu, const float* P, int64_t Bc, int64_t ldp, int D,
-                               int64_t row_base, float inv_count, float inv_temperature, float* dU, int64_t ld_du,
-                               float* dP, int64_t ld_dp, double* loss_sum, void* ws, size_t ws_bytes, hipStream_t s);
-size_t inbatch_softmax_loss_workspace_bytes(int64_t B, int64_t Bc, int D);
-int inbatch_softmax_loss_standalone(const float* U, int64_t B, int64_t ldu, const float* P, int64_t Bc, int64_t ldp,
-                                    int D, int64_t row_base, float inv_temperature, double* loss_sum, void* ws,
-                                    size_t ws_bytes, hipStream_t s);
+// The four one-call ops of the C ABI (ttamm_inbatch_bce, _bce_loss, _softmax, _softmax_loss): loss =
+// TTAMM_INBATCH_BCE / _SOFTMAX, grads = with dU / dP (the loss-only forms take neither, nor inv_count;
+// inv_temperature is read under softmax only).  One argument check, one workspace binder, the loss
+// summed into loss_sum.
+size_t inbatch_op_workspace_bytes(int loss, bool grads, int64_t B, int64_t Bc, int D);
+int inbatch_op(int loss, bool grads, const InBatchProblem& p, float inv_count, float inv_temperature, float* dU,
+               int64_t ld_du, float* dP, int64_t ld_dp, double* loss_sum, void* ws, size_t ws_bytes, hipStream_t s);
 
 // ------------------------------------------------------------------------------------
 // Exact inner-product retrieval + top-k (retrieval.hip)

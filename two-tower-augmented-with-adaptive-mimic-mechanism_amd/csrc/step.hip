@@ -844,19 +844,13 @@ InBatchArgs& bind_inbatch(Step& st) {
     const bool shard = sharded(A);
     const int D = st.D;
     InBatchArgs& a = st.ws.ib;
-    a.U = st.ws.user.aug;
-    a.ldu = D;
-    a.B = st.B;
-    a.P = shard ? A.inbatch_items : st.ws.item.aug;  // one process: rows [0, B), the positives
-    a.dP = shard ? A.inbatch_dp_all : st.ws.ib_dp;
-    a.ldp = D;
-    a.ld_dp = D;
-    a.Bc = inbatch_cols(st);
-    a.D = D;
-    a.row_base = shard ? A.row_base : 0;
+    const float* P = shard ? A.inbatch_items : st.ws.item.aug;  // one process: rows [0, B), the positives
+    static_cast<InBatchProblem&>(a) = {st.ws.user.aug, D, st.B, P, D, inbatch_cols(st), D, shard ? A.row_base : 0};
     a.inv_T = 1.0f / (float)bce_count(st);
     a.dU = st.ws.ib_du;
     a.ld_du = D;
+    a.dP = shard ? A.inbatch_dp_all : st.ws.ib_dp;
+    a.ld_dp = D;
     return a;
 }
 int run_inbatch(Step& st, hipStream_t s) {
@@ -866,7 +860,7 @@ int run_inbatch(Step& st, hipStream_t s) {
     InBatchArgs& a = bind_inbatch(st);
     if (st.ws.ib_softmax) {  // the LSE pass (the rows' normalisers, the loss partials), then the softmax gradient kernel
         InBatchLossArgs& l = st.ws.ib_lse;
-        l.U = a.U, l.ldu = a.ldu, l.P = a.P, l.ldp = a.ldp, l.D = a.D, l.row_base = a.row_base;
+        static_cast<InBatchProblem&>(l) = a;
         if ((rc = launch_inbatch_softmax(a, l, st.A.in_batch_inv_temperature, s))) return rc;
     } else if ((rc = launch_inbatch(a, s))) {
         return rc;
