@@ -89,34 +89,37 @@ __device__ __forceinline__ float4 mask4(float4 v, int c, int lim, int ld, int on
     return make_float4(t[0], t[1], t[2], t[3]);
 }
 
-// MF: MFMA block edge — 32 (v_mfma_f32_32x32x2_f32 / 32x32x16_bf16) or 16
-// (v_mfma_f32_16x16x4_f32, fp32 only): the 16-row granularity lets a tile height divide the
-// step's row count into exactly two tiles per CU (C2: 57344 = 512 x 112).
-template <int BM_, int BN_, int WAVES_M_, int WAVES_N_, bool A_KMAJ_, bool B_KMAJ_, int MF_ = 32>
-struct Cfg {
-    static constexpr int BM = BM_, BN = BN_, WAVES_M = WAVES_M_, WAVES_N = WAVES_N_, MF = MF_;
+// Epilogue geometry of a BM x BN tile of WAVES_M wave rows, each I MFMA row blocks high (the base
+// of Cfg and XCfg): the accumulators pass through LDS in row slices of whole MFMA row blocks —
+// halves of the tile by wave rows, or by row blocks when one wave row spans the tile.
+template <int BM, int BN, int WAVES_M, int I>
+struct EpiGeom {
+    static constexpr int CLD = BN + 4;  // epilogue tile row stride
+    static constexpr int EPI_ROWS = WAVES_M >= 2 ? BM / 2 : (I > 1 ? (I + 1) / 2 * 32 : BM);
+    static constexpr int EPI_PHASES = (BM + EPI_ROWS - 1) / EPI_ROWS;
+    static_assert(WAVES_M == 1 || WAVES_M % EPI_PHASES == 0, "epilogue slices must hold whole wave rows");
+};
+
+// Tile geometry of the fp32-MFMA kernel: 4 waves as WAVES_M x WAVES_N, each a TM x TN wave tile of
+// I x J 32 x 32 MFMA blocks (v_mfma_f32_32x32x2_f32 / 32x32x16_bf16).
+template <int BM_, int BN_, int WAVES_M_, int WAVES_N_, bool A_KMAJ_, bool B_KMAJ_>
+struct Cfg : EpiGeom<BM_, BN_, WAVES_M_, BM_ / WAVES_M_ / 32> {
+    using Epi = EpiGeom<BM_, BN_, WAVES_M_, BM_ / WAVES_M_ / 32>;
+    static constexpr int BM = BM_, BN = BN_, WAVES_M = WAVES_M_, WAVES_N = WAVES_N_;
     static constexpr bool A_KMAJ = A_KMAJ_, B_KMAJ = B_KMAJ_;
     static constexpr int TM = BM / WAVES_M, TN = BN / WAVES_N;
-    static constexpr int I = TM / MF, J = TN / MF;
-    static constexpr int NR = MF == 32 ? 16 : 4;  // accumulator registers per MFMA block
+    static constexpr int I = TM / 32, J = TN / 32;
     static constexpr int A_F4 = BM * BK / 4, B_F4 = BN * BK / 4;
     static constexpr int A_LOADS = (A_F4 + kThreads - 1) / kThreads;
     static constexpr int B_LOADS = (B_F4 + kThreads - 1) / kThreads;
     static constexpr int A_STAGE = A_KMAJ ? BK * BM : BM * SK;  // floats per buffer
     static constexpr int B_STAGE = B_KMAJ ? BK * BN : BN * SK;
     static constexpr int STAGE = 2 * (A_STAGE + B_STAGE);
-    static constexpr int CLD = BN + 4;                           // epilogue tile row stride
-    // epilogue row slices (whole MFMA row blocks): halves of the tile by wave rows, or by
-    // row blocks when one wave row spans the tile
-    static constexpr int EPI_ROWS = WAVES_M >= 2 ? BM / 2 : (I > 1 ? (I + 1) / 2 * MF : BM);
-    static constexpr int EPI_PHASES = (BM + EPI_ROWS - 1) / EPI_ROWS;
-    static constexpr int EPI = EPI_ROWS * CLD;
+    static constexpr int EPI = Epi::EPI_ROWS * Epi::CLD;
     static constexpr int KIDX = A_KMAJ ? 2 * kWgradMaxRowsPerSplit : 0;  // int64 gather rows (floats)
     static constexpr int LDS = (STAGE + KIDX) > EPI ? (STAGE + KIDX) : EPI;
     static_assert(WAVES_M * WAVES_N == 4, "4 waves per block");
-    static_assert(MF == 32 || MF == 16, "MFMA block edge");
-    static_assert(TM % MF == 0 && TN % MF == 0, "wave tile must be a multiple of the MFMA block");
-    static_assert(WAVES_M == 1 || WAVES_M % EPI_PHASES == 0, "epilogue slices must hold whole wave rows");
+    static_assert(TM % 32 == 0 && TN % 32 == 0, "wave tile must be a multiple of the MFMA block");
 };
 
 // ---- the fused elementwise tail on 4 consecutive columns of one row ----------------------
@@ -329,14 +332,37 @@ __device__ __forceinline__ void epilogue8_hidden(const KArg(GemmProblem) & P, fl
     if (hi_ok) *reinterpret_cast<float4*>(out + 4) = make_float4(x[4], x[5], x[6], x[7]);
 }
 
+// ---- pieces the three kernels share, and those that stay inline ------------------------------
+// (The problem / tile decode stays inline in the three kernels.  As one tile_of<BM, BN> helper it held
+// every resource line, but gemm_bf16_kernel, which has no row split, gained the split division
+// (1084 -> 1108 instructions) and its EPI_STORE launch measured 67.1 -> 68.2 us, outside the parent's
+// 66.6 - 67.4; the split-bf16 forward moved 90.5 -> 92.2 us against 90.2 - 91.4.)
+// (The accumulator spill of an epilogue phase into Cs stays inline in the three kernels.  As one
+// helper over the wave's blocks it moved the 128 x 192 pre-split forward kernel's scratch from 28 to
+// 32 B, 8 -> 9 spilled VGPRs; as a helper per MFMA block it held every resource figure but the
+// phase loop then unrolled: gemm_bf16_kernel<EPI_STORE> 1084 -> 1624 instructions, the fp32-MFMA
+// 128 x 96 EPI_DGRAD_HIDDEN kernels 5147 -> 8763.)
+
+// The bias of a 4-column group under the generic epilogue4<E> row loops: the forward epilogues add
+// one when the problem has one, the dgrad epilogues none (zero).  (The row loops themselves, and the
+// lane-pair EPI_HIDDEN loop, stay in each kernel: as shared helpers, with M and N read from the
+// problem or bound by the caller, they moved the SGPR spill counts of 11 split kernels, e.g. the
+// 128 x 192 bf16 dgrad kernels' 85 -> 90 and the bf16 wide weight gradient's 26 -> 29.)
+template <int E>
+__device__ __forceinline__ float4 bias4_of(const KArg(GemmProblem) & P, int col) {
+    constexpr bool kBiased = E == EPI_STORE || E == EPI_HIDDEN || E == EPI_GATE_HIDDEN || E == EPI_GATE_OUT;
+    const bool has_bias = kBiased && P.bias != nullptr;
+    return has_bias ? ld4(P.bias + col) : make_float4(0.f, 0.f, 0.f, 0.f);
+}
+
 template <class CF, int E, bool BF>
 __global__ __launch_bounds__(kThreads) void gemm_kernel(GemmBatch batch) {
     constexpr int BM = CF::BM, BN = CF::BN, TM = CF::TM, TN = CF::TN, I = CF::I, J = CF::J;
     constexpr bool AK = CF::A_KMAJ, BKM = CF::B_KMAJ;
     __shared__ __attribute__((aligned(16))) float lds[CF::LDS];
 
-    // ---- problem / tile --------------------------------------------------------------------
     const KArg(GemmBatch)* kb = (const KArg(GemmBatch)*)(__builtin_amdgcn_kernarg_segment_ptr());
+    // ---- problem / tile --------------------------------------------------------------------
     int tile = blockIdx.x;
     int pi = 0;
 #pragma unroll 1
@@ -349,16 +375,14 @@ __global__ __launch_bounds__(kThreads) void gemm_kernel(GemmBatch batch) {
     tile -= split * tiles_mn;
     const int tm = tile / P.tiles_n, tn = tile - tm * P.tiles_n;
     const int m0 = tm * BM, n0 = tn * BN;
-    const int M = P.M, N = P.N;
     const int k_begin = split * P.k_split;
     const int k_end = min(P.K, k_begin + P.k_split);
+    const int M = P.M, N = P.N;
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int wm = wave / CF::WAVES_N, wn = wave % CF::WAVES_N;
-    constexpr int MF = CF::MF;
-    // lane -> (row/column in an MFMA block, k slot): 32x32x2 has 2 k slots of 32 lanes,
-    // 16x16x4 has 4 k slots of 16 lanes
-    const int li = lane & (MF - 1), h = lane / MF;
+    // lane -> (row/column in an MFMA block, k slot): 32x32x2 has 2 k slots of 32 lanes
+    const int li = lane & 31, h = lane / 32;
     float* As = lds;
     float* Bs = lds + 2 * CF::A_STAGE;
 
@@ -407,14 +431,13 @@ __global__ __launch_bounds__(kThreads) void gemm_kernel(GemmBatch batch) {
         else b_rp[it] = P.B + (int64_t)(lin / (BN / 4)) * P.ldb + n0 + (lin % (BN / 4)) * 4;
     }
 
-    using Acc = std::conditional_t<MF == 32, f32x16, f32x4_t>;
-    Acc acc[I][J];
+    f32x16 acc[I][J];
 #pragma unroll
     for (int i = 0; i < I; ++i)
 #pragma unroll
         for (int j = 0; j < J; ++j)
 #pragma unroll
-            for (int r = 0; r < CF::NR; ++r) acc[i][j][r] = 0.f;
+            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
 
     auto mainloop = [&](auto fast_tag) {
         constexpr bool FAST = decltype(fast_tag)::value;
@@ -487,37 +510,22 @@ __global__ __launch_bounds__(kThreads) void gemm_kernel(GemmBatch batch) {
             constexpr int buf = decltype(S)::value;
             const float* as = As + buf * CF::A_STAGE;
             const float* bs = Bs + buf * CF::B_STAGE;
-            // the lane's 4 k values kb .. kb+3 of A row m / B column n, kb = 8h + 4*s4 (32x32:
-            // lane half h walks k = 8h..8h+7) or 4h (16x16: k slot h walks k = 4h..4h+3)
-            auto kbase = [&](int s4) { return MF == 32 ? 8 * h + 4 * s4 : 4 * h; };
+            // the lane's 4 k values kb .. kb+3 of A row m / B column n, kb = 8h + 4*s4 (lane half
+            // h walks k = 8h..8h+7)
+            auto kbase = [&](int s4) { return 8 * h + 4 * s4; };
             auto frag_a = [&](int i, int s4) -> float4 {
-                const int m = wm * TM + i * MF + li;
+                const int m = wm * TM + i * 32 + li;
                 if (!AK) return *reinterpret_cast<const float4*>(as + m * SK + kbase(s4));
                 const float* c = as + kbase(s4) * BM + m;
                 return make_float4(c[0], c[BM], c[2 * BM], c[3 * BM]);
             };
             auto frag_b = [&](int j, int s4) -> float4 {
-                const int n = wn * TN + j * MF + li;
+                const int n = wn * TN + j * 32 + li;
                 if (!BKM) return *reinterpret_cast<const float4*>(bs + n * SK + kbase(s4));
                 const float* c = bs + kbase(s4) * BN + n;
                 return make_float4(c[0], c[BN], c[2 * BN], c[3 * BN]);
             };
-            if constexpr (MF == 16) {
-                static_assert(!BF, "16x16 blocks are fp32 only");
-                float4 af[I], bf[J];
-#pragma unroll
-                for (int i = 0; i < I; ++i) af[i] = frag_a(i, 0);
-#pragma unroll
-                for (int j = 0; j < J; ++j) bf[j] = frag_b(j, 0);
-#pragma unroll
-                for (int q = 0; q < 4; ++q)
-#pragma unroll
-                    for (int i = 0; i < I; ++i)
-#pragma unroll
-                        for (int j = 0; j < J; ++j)
-                            acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(f4get(af[i], q), f4get(bf[j], q),
-                                                                             acc[i][j], 0, 0, 0);
-            } else if constexpr (BF) {
+            if constexpr (BF) {
                 bf16x8 a8[I], b8[J];
 #pragma unroll
                 for (int i = 0; i < I; ++i) a8[i] = pack_bf16(frag_a(i, 0), frag_a(i, 1));
@@ -562,23 +570,17 @@ __global__ __launch_bounds__(kThreads) void gemm_kernel(GemmBatch batch) {
         // one step on LDS buffer B: DEEP — prefetch k-tile kt+2 into register set B (its LDS
         // buffer is free after the barrier), compute kt, write kt+1 (set NB) to buffer NB;
         // shallow — prefetch kt+1 into set 0, compute kt, write set 0 to buffer NB
+        // (developer ablation 1: no k-loop traffic, which measures the MFMA / LDS loop)
+        constexpr bool TRAFFIC = TTAMM_GEMM_ABLATE != 1;
         auto step = [&](auto Bf, auto NB, int kt) {
             if constexpr (DEEP) {
-#if TTAMM_GEMM_ABLATE != 1  // developer ablation 1: no k-loop traffic (measures the MFMA/LDS loop)
-                if (kt + 2 < nk) load_tile(Bf, kof(kt + 2));
-#endif
+                if (TRAFFIC && kt + 2 < nk) load_tile(Bf, kof(kt + 2));
                 compute(Bf);
-#if TTAMM_GEMM_ABLATE != 1
-                if (kt + 1 < nk) store_tile(NB, NB, kof(kt + 1));
-#endif
+                if (TRAFFIC && kt + 1 < nk) store_tile(NB, NB, kof(kt + 1));
             } else {
-#if TTAMM_GEMM_ABLATE != 1
-                if (kt + 1 < nk) load_tile(S0{}, kof(kt + 1));
-#endif
+                if (TRAFFIC && kt + 1 < nk) load_tile(S0{}, kof(kt + 1));
                 compute(Bf);
-#if TTAMM_GEMM_ABLATE != 1
-                if (kt + 1 < nk) store_tile(S0{}, NB, kof(kt + 1));
-#endif
+                if (TRAFFIC && kt + 1 < nk) store_tile(S0{}, NB, kof(kt + 1));
             }
             __syncthreads();
         };
@@ -599,14 +601,14 @@ __global__ __launch_bounds__(kThreads) void gemm_kernel(GemmBatch batch) {
         const int rows_here = min(CF::EPI_ROWS, BM - row_lo);
 #pragma unroll
         for (int i = 0; i < I; ++i) {
-            const int br = wm * TM + i * MF;  // first tile row of MFMA row block i
+            const int br = wm * TM + i * 32;
             if (br < row_lo || br >= row_lo + CF::EPI_ROWS) continue;
 #pragma unroll
             for (int j = 0; j < J; ++j)
 #pragma unroll
-                for (int r = 0; r < CF::NR; ++r) {
-                    const int rr = br - row_lo + (MF == 32 ? (r & 3) + 8 * (r >> 2) + 4 * h : 4 * h + r);
-                    Cs[rr * CF::CLD + wn * TN + j * MF + li] = acc[i][j][r];
+                for (int r = 0; r < 16; ++r) {
+                    const int rr = br - row_lo + (r & 3) + 8 * (r >> 2) + 4 * h;
+                    Cs[rr * CF::CLD + wn * TN + j * 32 + li] = acc[i][j][r];
                 }
         }
         __syncthreads();
@@ -636,9 +638,7 @@ __global__ __launch_bounds__(kThreads) void gemm_kernel(GemmBatch batch) {
             const int c4 = tid % C4, r0 = tid / C4;
             const int col = n0 + c4 * 4;
             if (r0 < RSTEP && col < N) {
-                const bool has_bias = (E == EPI_STORE || E == EPI_HIDDEN || E == EPI_GATE_HIDDEN || E == EPI_GATE_OUT) &&
-                                      P.bias != nullptr;
-                const float4 bias4 = has_bias ? ld4(P.bias + col) : make_float4(0.f, 0.f, 0.f, 0.f);
+                const float4 bias4 = bias4_of<E>(P, col);
 #pragma unroll 4
                 for (int rr = r0; rr < rows_here; rr += RSTEP) {
                     const int row = m0 + row_lo + rr;
@@ -671,8 +671,9 @@ __global__ __launch_bounds__(kThreads) void gemm_kernel(GemmBatch batch) {
 //                     two ds_read_b64_tr_b16 (hardware transpose: lane i of a 16-lane group gets
 //                     column i of a 4 x 16 block), conflict-free per 32-lane half.
 template <int BM_, int BN_, int WAVES_M_, int WAVES_N_, bool A_KMAJ_, bool B_KMAJ_, int KT_ = 16, int AD_ = 2,
-          bool APL_ = false, bool A16_ = false>
-struct XCfg {
+          bool APL_ = false>
+struct XCfg : EpiGeom<BM_, BN_, WAVES_M_, BM_ / WAVES_M_ / 32> {
+    using Epi = EpiGeom<BM_, BN_, WAVES_M_, BM_ / WAVES_M_ / 32>;
     static constexpr int BM = BM_, BN = BN_, WAVES_M = WAVES_M_, WAVES_N = WAVES_N_;
     static constexpr bool A_KMAJ = A_KMAJ_, B_KMAJ = B_KMAJ_;
     static constexpr int KT = KT_;     // k per tile: 16 (three planes) or 32 (bf16, one plane)
@@ -680,16 +681,13 @@ struct XCfg {
     // A pre-split in memory (GemmProblem::A3p: [row][k / 16][hi, mid, lo][16] bf16, the feature rows
     // split once): staged as 16-B pieces of the three planes, no split arithmetic in the loop
     static constexpr bool APL = APL_;
-    // A16: K-major A already bf16 in memory (GemmProblem::A16 / lda16, rows gathered by a_idx; the bf16
-    // towers' feature copy): 16-B pieces of 8 columns straight into the plane, no conversion
-    static constexpr bool A16 = A16_;
-    static_assert(!A16 || (A_KMAJ_ && KT_ == 32 && !APL_), "bf16 A: K-major, one plane (32-k tiles)");
     static constexpr int RB = KT * 2;  // MN-major row bytes
     static constexpr int TM = BM / WAVES_M, TN = BN / WAVES_N, I = TM / 32, J = TN / 32;
-    // blocks per CU the register budget is planned for: wave tiles of 8 or more accumulator tiles
-    // (128 registers and up) run one wave per SIMD with the whole register file
-    static constexpr int MINB = I * J >= 8 ? 1 : 2;
-    static constexpr int A_F4 = APL ? BM * KT * 6 / 16 : (A16 ? BM * KT / 8 : BM * KT / 4), B_F4 = BN * KT / 4;
+    // blocks per CU the register budget is planned for (every wave tile has at most 6 accumulator
+    // tiles; 8 or more, 128 registers and up, would need the whole register file)
+    static constexpr int MINB = 2;
+    static_assert(I * J < 8, "wave tiles of 8 accumulator tiles do not fit two blocks per CU");
+    static constexpr int A_F4 = APL ? BM * KT * 6 / 16 : BM * KT / 4, B_F4 = BN * KT / 4;
     static_assert(!APL || KT == 16, "A planes: 16-k tiles (one 96-byte chunk per row and k-tile)");
     static constexpr int A_LOADS = (A_F4 + kThreads - 1) / kThreads;
     static constexpr int B_LOADS = (B_F4 + kThreads - 1) / kThreads;
@@ -703,21 +701,17 @@ struct XCfg {
     static constexpr int A_PLANE = A_KMAJ ? KT * SA : BM * RB;  // bytes
     static constexpr int B_PLANE = B_KMAJ ? KT * SB : BN * RB;
     static_assert(KT == 16 || KT == 32, "k tile of 16 or 32");
-    static constexpr int CLD = BN + 4;
-    static constexpr int EPI_ROWS = WAVES_M >= 2 ? BM / 2 : (I > 1 ? (I + 1) / 2 * 32 : BM);
-    static constexpr int EPI_PHASES = (BM + EPI_ROWS - 1) / EPI_ROWS;
     // K-major A: the split's (gathered) row ids as int32 (tables < 2^31 rows): 4 KB, so the
     // 128 x 96 weight-gradient tile fits three blocks per CU (53,248 B of LDS each)
     static constexpr int KIDX_BYTES = A_KMAJ ? 4 * kWgradMaxRowsPerSplit : 0;
     static constexpr int buf_bytes(int pl) { return pl * (A_PLANE + B_PLANE); }
     static constexpr int lds_bytes(int pl) {
-        const int st = 2 * buf_bytes(pl) + KIDX_BYTES, ep = EPI_ROWS * CLD * 4;
+        const int st = 2 * buf_bytes(pl) + KIDX_BYTES, ep = Epi::EPI_ROWS * Epi::CLD * 4;
         return st > ep ? st : ep;
     }
     static_assert(WAVES_M * WAVES_N == 4, "4 waves per block");
     static_assert(TM % 32 == 0 && TN % 32 == 0, "wave tile must be a multiple of 32");
     static_assert(A_F4 % kThreads == 0, "whole A staging rounds");
-    static_assert(WAVES_M == 1 || WAVES_M % EPI_PHASES == 0, "epilogue slices must hold whole wave rows");
 };
 
 typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
@@ -729,9 +723,6 @@ typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
 #ifndef TTAMM_X_ABLATE
 #define TTAMM_X_ABLATE 0
 #endif
-#ifndef TTAMM_SPLIT8
-#define TTAMM_SPLIT8 0
-#endif
 // The mid x mid partial product (|mid| <= 2^-9 |x|, so <= 2^-18 of |ab|): kept (six products).
 // Without it (-DTTAMM_SPLIT_MM=0, five) the GEMMs ran 1.2-1.5 % faster at C2 but their error
 // against fp64 tripled (max |err| / max |C| 9.4e-7 -> 2.7e-6 on layer 1, fp32 MFMA 9.5e-7) and the
@@ -739,14 +730,6 @@ typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
 // kernel, whose errors did not move, takes five (inbatch.hip TTAMM_IB_PRODUCTS)
 #ifndef TTAMM_SPLIT_MM
 #define TTAMM_SPLIT_MM 1
-#endif
-#ifndef TTAMM_BF16_DEEP
-#define TTAMM_BF16_DEEP 1
-#endif
-// The dgrad epilogue's aux0 rows loaded a phase at a time ahead of the Cs barrier (gemm_x_kernel);
-// -DTTAMM_DGRAD_PREFETCH=0: the loads inside the row loop, for A/B runs
-#ifndef TTAMM_DGRAD_PREFETCH
-#define TTAMM_DGRAD_PREFETCH 1
 #endif
 // x -> (hi, mid, lo) bf16 quadruples, 8 bytes each
 template <int PL>
@@ -825,14 +808,17 @@ __global__ __launch_bounds__(kThreads, CX::MINB) void gemm_x_kernel(GemmBatch ba
     tile -= split * tiles_mn;
     const int tm = tile / P.tiles_n, tn = tile - tm * P.tiles_n;
     const int m0 = tm * BM, n0 = tn * BN;
-    const int M = P.M, N = P.N;
     const int k_begin = split * P.k_split;
     const int k_end = min(P.K, k_begin + P.k_split);
+    const int M = P.M, N = P.N;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int wm = wave / CX::WAVES_N, wn = wave % CX::WAVES_N;
     const int li = lane & 31, h = lane >> 5;
 
     // staging maps: MN-major thread -> (row lin / 4, k 4 * (lin % 4)); K-major -> (k row, 4 mn)
+    // (the fp32 maps, b_rp and `fast` repeat gemm_kernel's: as helpers shared with it they moved the
+    // SGPR spill counts of the pre-split 128 x 192 forward kernel, 16 -> 17, and the 128 x 96 bf16
+    // dgrad kernel, 4 -> 2)
     const float* a_rp[CX::A_LOADS];
     bool a_ok[CX::A_LOADS];
     int a_r[CX::A_LOADS], a_c[CX::A_LOADS];
@@ -863,11 +849,6 @@ __global__ __launch_bounds__(kThreads, CX::MINB) void gemm_x_kernel(GemmBatch ba
                 ap_rp[it] = P.A3p;
                 ap_lds[it] = pl * CX::A_PLANE + a_r[it] * CX::SA + (ch * 16 + hf * 8) * 2;
             }
-            a_rp[it] = nullptr;
-        } else if constexpr (CX::A16) {  // k row lin / (BM / 8), columns 8 (lin % (BM / 8)) .. + 7
-            a_r[it] = lin / (BM / 8);
-            a_c[it] = (lin % (BM / 8)) * 8;
-            a_ok[it] = m0 + a_c[it] < P.a_cols;  // the copy is zero from a_cols to its row end
             a_rp[it] = nullptr;
         } else if (!AK) {
             a_r[it] = lin / (KT / 4);
@@ -923,12 +904,14 @@ __global__ __launch_bounds__(kThreads, CX::MINB) void gemm_x_kernel(GemmBatch ba
     // written to LDS between the current tile's MFMAs.  32-k tiles with more accumulators (128 x 192)
     // keep one set (the register budget), loaded at a step's start and written after its MFMAs —
     // one k-tile of MFMAs (8-12 per wave) cannot hide an HBM load, which left C5's bf16 GEMMs
-    // latency-bound (build with -DTTAMM_BF16_DEEP=0 for one set everywhere)
-    constexpr bool XDEEP = KT == 16 || (I * J <= 4 && TTAMM_BF16_DEEP);
+    // latency-bound
+    constexpr bool XDEEP = KT == 16 || I * J <= 4;
     // A3: A in three register sets, loaded two k-tiles ahead (B, L2-resident weights or dY, one)
     constexpr bool A3 = XDEEP && CX::AD == 3;
     float4 ra[XDEEP ? (A3 ? 3 : 2) : 1][CX::A_LOADS], rb[XDEEP ? 2 : 1][CX::B_LOADS];
 
+    // (developer ablation 3: no k-loop traffic after the first tiles — MFMA + LDS reads only)
+    constexpr bool TRAFFIC = TTAMM_X_ABLATE != 3;
     auto mainloop = [&](auto fast_tag) {
         constexpr bool FAST = decltype(fast_tag)::value;
         auto load_a = [&](auto S, int k0) {
@@ -945,12 +928,6 @@ __global__ __launch_bounds__(kThreads, CX::MINB) void gemm_x_kernel(GemmBatch ba
                         const uint16_t* rp = P.A3p + (int64_t)kidx[k - k_begin] * P.lda3 + (m0 >> 4) * 48;
                         ra[R][it] = *reinterpret_cast<const float4*>(rp + a_c[it]);
                     }
-                    continue;
-                }
-                if constexpr (CX::A16) {
-                    const int k = FAST ? k0 + a_r[it] : min(k0 + a_r[it], k_end - 1);
-                    const uint16_t* rp = P.A16 + (int64_t)kidx[k - k_begin] * P.lda16 + m0 + a_c[it];
-                    ra[R][it] = (FAST || a_ok[it]) ? *reinterpret_cast<const float4*>(rp) : make_float4(0.f, 0.f, 0.f, 0.f);
                     continue;
                 }
                 if (!AK) {
@@ -1000,7 +977,6 @@ __global__ __launch_bounds__(kThreads, CX::MINB) void gemm_x_kernel(GemmBatch ba
                 if constexpr (CX::APL) {
                     // a pre-split piece: straight into its plane (rows past M / k rows past the split
                     // and chunks past the row's planes are zero)
-                    unsigned char* Ap2 = lds + decltype(Buf)::value * CX::buf_bytes(PL);
                     const bool ok = AK ? (a_ok[it] && (FAST || k0 + a_r[it] < k_end)) : (FAST || a_ok[it]);
                     // a value select per component (a select of the two float4 objects compiled to a
                     // select of their addresses: both spilled to scratch)
@@ -1025,14 +1001,7 @@ __global__ __launch_bounds__(kThreads, CX::MINB) void gemm_x_kernel(GemmBatch ba
                                             __uint_as_float(w4[3]));
                         }
                     }
-                    *reinterpret_cast<float4*>(Ap2 + ap_lds[it]) = v;
-                    return;
-                }
-                if constexpr (CX::A16) {  // eight bf16 columns of k row a_r (zero past the split's rows)
-                    const bool ok = FAST || k0 + a_r[it] < k_end;
-                    const float4 r = ra[RA][it];
-                    const float4 v = make_float4(ok ? r.x : 0.f, ok ? r.y : 0.f, ok ? r.z : 0.f, ok ? r.w : 0.f);
-                    *reinterpret_cast<float4*>(Ap + a_r[it] * CX::SA + a_c[it] * 2) = v;
+                    *reinterpret_cast<float4*>(Ap + ap_lds[it]) = v;
                     return;
                 }
                 if (!AK) {
@@ -1105,10 +1074,6 @@ __global__ __launch_bounds__(kThreads, CX::MINB) void gemm_x_kernel(GemmBatch ba
 #pragma unroll
                 for (int pq = 0; pq < NP; ++pq) {
                     const int i = pq / J, j = pq % J;
-                    if constexpr (PL == 3 && TTAMM_SPLIT8) {  // developer: the 2^-24 terms ml, lm too
-                        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[1][i], bf[2][j], acc[i][j], 0, 0, 0);
-                        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[2][i], bf[1][j], acc[i][j], 0, 0, 0);
-                    }
                     if constexpr (PL == 3 && TTAMM_X_ABLATE != 2) {  // small terms first (ablation 2: hh only)
                         if constexpr (TTAMM_SPLIT_MM)  // mid x mid (<= 2^-18 relative; not kept by default)
                             acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[1][i], bf[1][j], acc[i][j], 0, 0, 0);
@@ -1118,14 +1083,12 @@ __global__ __launch_bounds__(kThreads, CX::MINB) void gemm_x_kernel(GemmBatch ba
                         acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[0][i], bf[1][j], acc[i][j], 0, 0, 0);
                     }
                     acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[0][i], bf[0][j], acc[i][j], 0, 0, 0);
-#if TTAMM_X_ABLATE != 3
-                    if constexpr (XDEEP) {
+                    if constexpr (XDEEP && TRAFFIC) {
                         const int slot = ks * NP + pq;
 #pragma unroll
                         for (int q = (slot * NITEMS) / NSLOT; q < ((slot + 1) * NITEMS) / NSLOT; ++q)
                             store_item2(SA, SB, NB, q, k0n, fresh);
                     }
-#endif
                 }
             }
         };
@@ -1142,13 +1105,9 @@ __global__ __launch_bounds__(kThreads, CX::MINB) void gemm_x_kernel(GemmBatch ba
             store_tile(S0{}, S0{}, kof(0), true);
             __syncthreads();
             auto sstep = [&](auto Buf, auto NB, int kt) {
-#if TTAMM_X_ABLATE != 3
-                load_tile(S0{}, kof(kt + 1));
-#endif
+                if constexpr (TRAFFIC) load_tile(S0{}, kof(kt + 1));
                 compute(Buf, S0{}, NB, kof(kt + 1), kt + 1 < nk);
-#if TTAMM_X_ABLATE != 3
-                store_tile(S0{}, NB, kof(kt + 1), kt + 1 < nk);
-#endif
+                if constexpr (TRAFFIC) store_tile(S0{}, NB, kof(kt + 1), kt + 1 < nk);
                 __syncthreads();
             };
             int kt = 0;
@@ -1174,10 +1133,10 @@ __global__ __launch_bounds__(kThreads, CX::MINB) void gemm_x_kernel(GemmBatch ba
                 using NB = std::integral_constant<int, (i + 1) & 1>;
                 using LA = std::integral_constant<int, i % 3>;
                 using SA = std::integral_constant<int, (i + 1) % 3>;
-#if TTAMM_X_ABLATE != 3
-                load_a(LA{}, kof(kt + 3));
-                load_b(Buf{}, kof(kt + 2));
-#endif
+                if constexpr (TRAFFIC) {
+                    load_a(LA{}, kof(kt + 3));
+                    load_b(Buf{}, kof(kt + 2));
+                }
                 compute2(Buf{}, SA{}, NB{}, NB{}, kof(kt + 1), kt + 1 < nk);
                 __syncthreads();
             };
@@ -1204,9 +1163,7 @@ __global__ __launch_bounds__(kThreads, CX::MINB) void gemm_x_kernel(GemmBatch ba
             // kt left (already in LDS), multiply kt while splitting kt + 1 into the other buffer
             // (last read in k-tile kt - 1, before that tile's barrier).
             auto step = [&](auto Bf, auto NB, int kt) {
-#if TTAMM_X_ABLATE != 3  // developer ablation 3: no k-loop traffic (MFMA + LDS reads only)
-                load_tile(Bf, kof(kt + 2));
-#endif
+                if constexpr (TRAFFIC) load_tile(Bf, kof(kt + 2));
                 compute(Bf, NB, NB, kof(kt + 1), kt + 1 < nk);
                 __syncthreads();
             };
@@ -1254,7 +1211,7 @@ __global__ __launch_bounds__(kThreads, CX::MINB) void gemm_x_kernel(GemmBatch ba
     // publishes Cs — and, where two sets fit the register budget (PRE2), the next phase's before
     // this phase's row loop — instead of unroll-by-4 batches of dependent loads inside it.
     constexpr int PC4 = BN / 4, PRSTEP = kThreads / PC4;
-    constexpr bool PRE = TTAMM_DGRAD_PREFETCH && E == EPI_DGRAD_HIDDEN;
+    constexpr bool PRE = E == EPI_DGRAD_HIDDEN;
     constexpr int PRE_ROWS = PRE ? (CX::EPI_ROWS + PRSTEP - 1) / PRSTEP : 1;
     constexpr bool PRE2 = PRE && PRE_ROWS <= 8 && CX::EPI_PHASES > 1;
     float4 hv_cur[PRE_ROWS] = {}, hv_nxt[PRE_ROWS] = {};
@@ -1314,9 +1271,7 @@ __global__ __launch_bounds__(kThreads, CX::MINB) void gemm_x_kernel(GemmBatch ba
             if constexpr (PRE2)
                 if (ph + 1 < CX::EPI_PHASES) prefetch(ph + 1, hv_nxt);
             if (r0 < RSTEP && col < N) {
-                const bool has_bias = (E == EPI_STORE || E == EPI_HIDDEN || E == EPI_GATE_HIDDEN || E == EPI_GATE_OUT) &&
-                                      P.bias != nullptr;
-                const float4 bias4 = has_bias ? ld4(P.bias + col) : make_float4(0.f, 0.f, 0.f, 0.f);
+                const float4 bias4 = bias4_of<E>(P, col);
                 if (PRE && pre) {  // the rows prefetch() loaded, under its conditions
 #pragma unroll
                     for (int k = 0; k < PRE_ROWS; ++k) {
@@ -1371,7 +1326,7 @@ __global__ __launch_bounds__(kB16Threads) void gemm_bf16_kernel(GemmBatch batch)
         if (tile >= kb->p[q].tile_begin) pi = q;
     const KArg(GemmProblem)& P = kb->p[pi];
     tile -= P.tile_begin;
-    const int tm = tile / P.tiles_n, tn = tile - tm * P.tiles_n;
+    const int tm = tile / P.tiles_n, tn = tile - tm * P.tiles_n;  // (forward only: one split)
     const int m0 = tm * kB16M, n0 = tn * kB16N;
     const int M = P.M, N = P.N, K = P.K;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -1437,9 +1392,8 @@ __global__ __launch_bounds__(kB16Threads) void gemm_bf16_kernel(GemmBatch batch)
     __syncthreads();
     for (int kt = 0; kt < nk; ++kt) {
         const int buf = kt & 1;
-#if TTAMM_B16_ABLATE != 2  // developer ablation 2: no k-loop loads (MFMA + LDS only)
-        if (kt + 1 < nk) load((kt + 1) * kB16K);  // in flight during this k-tile's MFMAs
-#endif
+        // in flight during this k-tile's MFMAs (developer ablation 2: no k-loop loads, MFMA + LDS only)
+        if (TTAMM_B16_ABLATE != 2 && kt + 1 < nk) load((kt + 1) * kB16K);
         const uint16_t* as = lds + buf * kB16Stage;
         const uint16_t* bs = as + kB16M * kB16Ld;
 #pragma unroll
@@ -1507,17 +1461,14 @@ __global__ __launch_bounds__(kB16Threads) void gemm_bf16_kernel(GemmBatch batch)
             const int c4 = tid % C4, r0 = tid / C4;
             const int col = n0 + c4 * 4;
             if (col < N) {
-                const bool has_bias = (E == EPI_STORE || E == EPI_HIDDEN || E == EPI_GATE_HIDDEN || E == EPI_GATE_OUT) &&
-                                      P.bias != nullptr;
-                const float4 bias4 = has_bias ? ld4(P.bias + col) : make_float4(0.f, 0.f, 0.f, 0.f);
-    #pragma unroll 2
+                const float4 bias4 = bias4_of<E>(P, col);
+#pragma unroll 2
                 for (int rr = r0; rr < kB16EpiRows; rr += RSTEP) {
                     const int row = m0 + row_lo + rr;
-    #if TTAMM_B16_ABLATE == 1  // developer ablation 1: plain store instead of the fused tail
-                    if (row < M) st4(P.C + (int64_t)row * P.ldc + col, ld4(Cs + rr * kB16Cld + c4 * 4));
-    #else
-                    if (row < M) epilogue4<E>(P, ld4(Cs + rr * kB16Cld + c4 * 4), bias4, 0, row, col);
-    #endif
+                    if (row < M) {  // (developer ablation 1: a plain store instead of the fused tail)
+                        if constexpr (TTAMM_B16_ABLATE == 1) st4(P.C + (int64_t)row * P.ldc + col, ld4(Cs + rr * kB16Cld + c4 * 4));
+                        else epilogue4<E>(P, ld4(Cs + rr * kB16Cld + c4 * 4), bias4, 0, row, col);
+                    }
                 }
             }
         }
@@ -1602,87 +1553,66 @@ __global__ void wgrad_reduce_kernel(WgradBatch batch, int64_t total) {
     else if (P.grad_b) P.grad_b[m] = s;
 }
 
-template <class CF, int E, bool BF>
-int launch_one(GemmBatch& b, hipStream_t s) {
+// The one launcher of the three kernel templates: the batch's tile counts on bm x bn output tiles
+// (split-K problems: one set of tiles per k_split rows), then `kernel` on one block per tile.
+int launch_tiles(void (*kernel)(GemmBatch), int bm, int bn, int threads, GemmBatch& b, hipStream_t s) {
     int tiles = 0;
     for (int i = 0; i < b.count; ++i) {
         GemmProblem& p = b.p[i];
-        p.tiles_m = (int)ceil_div(p.M, CF::BM);
-        p.tiles_n = (int)ceil_div(p.N, CF::BN);
+        p.tiles_m = (int)ceil_div(p.M, bm);
+        p.tiles_n = (int)ceil_div(p.N, bn);
         if (p.k_split <= 0) p.k_split = p.K;
         p.tile_begin = tiles;
         tiles += p.tiles_m * p.tiles_n * (int)ceil_div(p.K, p.k_split);
     }
     b.total_tiles = tiles;
     if (tiles == 0) return TTAMM_OK;
-    hipLaunchKernelGGL((gemm_kernel<CF, E, BF>), dim3(tiles), dim3(kThreads), 0, s, b);
+    hipLaunchKernelGGL(kernel, dim3(tiles), dim3(threads), 0, s, b);
     TTAMM_LAUNCH_CHECK();
     return TTAMM_OK;
 }
-
-template <class CX, int E, int PL>
-int launch_one_x(GemmBatch& b, hipStream_t s) {
-    int tiles = 0;
-    for (int i = 0; i < b.count; ++i) {
-        GemmProblem& p = b.p[i];
-        p.tiles_m = (int)ceil_div(p.M, CX::BM);
-        p.tiles_n = (int)ceil_div(p.N, CX::BN);
-        if (p.k_split <= 0) p.k_split = p.K;
-        p.tile_begin = tiles;
-        tiles += p.tiles_m * p.tiles_n * (int)ceil_div(p.K, p.k_split);
-    }
-    b.total_tiles = tiles;
-    if (tiles == 0) return TTAMM_OK;
-    hipLaunchKernelGGL((gemm_x_kernel<CX, E, PL>), dim3(tiles), dim3(kThreads), 0, s, b);
-    TTAMM_LAUNCH_CHECK();
-    return TTAMM_OK;
-}
-template <class CX, int PL>
-int dispatch_epi_x(GemmBatch& b, hipStream_t s) {
+// The epilogue switch, written once: f(tag) with the batch's epilogue as a compile-time constant
+template <class F>
+int with_epilogue(const GemmBatch& b, F&& f) {
     switch (b.p[0].epi) {
-        case EPI_STORE: return launch_one_x<CX, EPI_STORE, PL>(b, s);
-        case EPI_HIDDEN: return launch_one_x<CX, EPI_HIDDEN, PL>(b, s);
-        case EPI_GATE_HIDDEN: return launch_one_x<CX, EPI_GATE_HIDDEN, PL>(b, s);
-        case EPI_GATE_OUT: return launch_one_x<CX, EPI_GATE_OUT, PL>(b, s);
-        case EPI_DGRAD_RELU: return launch_one_x<CX, EPI_DGRAD_RELU, PL>(b, s);
-        case EPI_DGRAD_GATE_EF: return launch_one_x<CX, EPI_DGRAD_GATE_EF, PL>(b, s);
-        case EPI_DGRAD_HIDDEN: return launch_one_x<CX, EPI_DGRAD_HIDDEN, PL>(b, s);
+        case EPI_STORE: return f(std::integral_constant<int, EPI_STORE>{});
+        case EPI_HIDDEN: return f(std::integral_constant<int, EPI_HIDDEN>{});
+        case EPI_GATE_HIDDEN: return f(std::integral_constant<int, EPI_GATE_HIDDEN>{});
+        case EPI_GATE_OUT: return f(std::integral_constant<int, EPI_GATE_OUT>{});
+        case EPI_DGRAD_RELU: return f(std::integral_constant<int, EPI_DGRAD_RELU>{});
+        case EPI_DGRAD_GATE_EF: return f(std::integral_constant<int, EPI_DGRAD_GATE_EF>{});
+        case EPI_DGRAD_HIDDEN: return f(std::integral_constant<int, EPI_DGRAD_HIDDEN>{});
         default: return fail(TTAMM_E_INVALID, "gemm: unknown epilogue");
     }
 }
+template <class CX, int PL>
+int dispatch_epi_x(GemmBatch& b, hipStream_t s) {
+    return with_epilogue(b, [&](auto e) {
+        return launch_tiles(gemm_x_kernel<CX, decltype(e)::value, PL>, CX::BM, CX::BN, kThreads, b, s);
+    });
+}
 // three planes on 16-k tiles (fp32 towers), or one plane on 32-k tiles (bf16 towers: twice the
 // MFMAs per barrier, the same LDS footprint)
-// fp32 towers, forward (weights MN-major): the A operand two k-tiles ahead (three register sets)
-// unless TTAMM_GEMM_ADEEP=2.  Alone the layer-1 forward runs 3 % slower that way (105 -> 108 us,
-// one spilled register), in the step beside the aux stream's gather and catch-up 6 % faster
-// (129 -> 122 us; C2 0.650 -> 0.641-0.644 ms, profiles/r04_gemm_adeep_s29.txt).  dgrad (K-major
-// weights, six k-tiles at C2) keeps two sets.
-template <int BM, int BN, int WM, int WN, bool AK, bool BK>
+// fp32 towers, forward (weights MN-major): the A operand two k-tiles ahead (three register sets).
+// Alone the layer-1 forward runs 3 % slower that way (105 -> 108 us, one spilled register), in
+// the step beside the aux stream's gather and catch-up 6 % faster (129 -> 122 us; C2 0.650 ->
+// 0.641-0.644 ms, profiles/r04_gemm_adeep_s29.txt).  dgrad (K-major weights, six k-tiles at C2)
+// keeps two sets.
+template <int BM, int BN, int WM, int WN, bool BKN>
 int dispatch_x(GemmBatch& b, hipStream_t s) {
-    static const bool adeep2 = [] {
-        const char* e = dev_env("TTAMM_GEMM_ADEEP");
-        return e && e[0] == '2';
-    }();
-    if (b.p[0].bf16) return dispatch_epi_x<XCfg<BM, BN, WM, WN, AK, BK, 32>, 1>(b, s);
-    if (adeep2 || AK || BK) return dispatch_epi_x<XCfg<BM, BN, WM, WN, AK, BK, 16>, 3>(b, s);
-    return dispatch_epi_x<XCfg<BM, BN, WM, WN, AK, BK, 16, 3>, 3>(b, s);
+    if (b.p[0].bf16) return dispatch_epi_x<XCfg<BM, BN, WM, WN, false, BKN, 32>, 1>(b, s);
+    return dispatch_epi_x<XCfg<BM, BN, WM, WN, false, BKN, 16, BKN ? 2 : 3>, 3>(b, s);
 }
 // Output tile width of a forward / dgrad launch: the width with the least padded output columns
 // over the batch (ties: the first listed).  Layer widths that are multiples of 128 but not of 192
 // (C4's 128 / 256, C5's 256 / 512) lost a third of the MFMA work to 128 x 192 tiles.  Latency-
 // bound launches (dgrad, or few 128-row tiles) take the narrow set, which keeps more blocks.
-int pick_tile_n(const GemmBatch& b, bool narrow, bool bf16) {
-    static const bool legacy = [] {
-        const char* e = dev_env("TTAMM_GEMM_TILES");
-        return e && std::strcmp(e, "legacy") == 0;
-    }();
+int pick_tile_n(const GemmBatch& b, bool narrow) {
     int maxN = 0;
     for (int i = 0; i < b.count; ++i) maxN = b.p[i].N > maxN ? b.p[i].N : maxN;
     if (maxN <= 96) return 96;
-    if (legacy) return narrow ? 96 : 192;
     // (128 x 256 tiles were built and measured: the bf16 kernel spills 200-350 B of scratch per
     // thread at two waves per SIMD; two 128-wide tiles cover 256 with no padding)
-    (void)bf16;
     static const int kNarrow[] = {96, 128};
     static const int kWide[] = {192, 128, 96};
     const int* c = narrow ? kNarrow : kWide;
@@ -1705,53 +1635,40 @@ bool exact_mfma() {
     return e && std::strcmp(e, "exact") == 0;
 }
 
-template <class CF, bool BF>
-int dispatch_epi_t(GemmBatch& b, hipStream_t s) {
-    switch (b.p[0].epi) {
-        case EPI_STORE: return launch_one<CF, EPI_STORE, BF>(b, s);
-        case EPI_HIDDEN: return launch_one<CF, EPI_HIDDEN, BF>(b, s);
-        case EPI_GATE_HIDDEN: return launch_one<CF, EPI_GATE_HIDDEN, BF>(b, s);
-        case EPI_GATE_OUT: return launch_one<CF, EPI_GATE_OUT, BF>(b, s);
-        case EPI_DGRAD_RELU: return launch_one<CF, EPI_DGRAD_RELU, BF>(b, s);
-        case EPI_DGRAD_GATE_EF: return launch_one<CF, EPI_DGRAD_GATE_EF, BF>(b, s);
-        case EPI_DGRAD_HIDDEN: return launch_one<CF, EPI_DGRAD_HIDDEN, BF>(b, s);
-        default: return fail(TTAMM_E_INVALID, "gemm: unknown epilogue");
-    }
-}
 template <class CF>
 int dispatch_epi(GemmBatch& b, hipStream_t s) {
-    if constexpr (CF::MF == 16) return dispatch_epi_t<CF, false>(b, s);
-    else return b.p[0].bf16 ? dispatch_epi_t<CF, true>(b, s) : dispatch_epi_t<CF, false>(b, s);
+    return with_epilogue(b, [&](auto e) {
+        constexpr int E = decltype(e)::value;
+        return launch_tiles(b.p[0].bf16 ? gemm_kernel<CF, E, true> : gemm_kernel<CF, E, false>, CF::BM, CF::BN, kThreads,
+                            b, s);
+    });
 }
 
-}  // namespace
+// What every forward / dgrad problem must satisfy, whichever kernel takes it; no split-K
+int prepare_forward(GemmProblem& p) {
+    TTAMM_REQUIRE(p.M >= 0 && p.N > 0 && p.K > 0, "gemm: bad shape");
+    TTAMM_REQUIRE(p.N % 4 == 0 && p.ldc % 4 == 0 && (uintptr_t)p.C % 16 == 0, "gemm: output must be float4-aligned");
+    p.k_split = p.K;
+    p.slab_stride = 0;
+    return TTAMM_OK;
+}
 
+// the bf16-operand kernel (GemmProblem::A16 / B16): EPI_STORE / EPI_HIDDEN
 int launch_gemm_bf16(GemmBatch& b, hipStream_t s) {
-    int tiles = 0;
     for (int i = 0; i < b.count; ++i) {
         GemmProblem& p = b.p[i];
-        TTAMM_REQUIRE(p.A16 && p.B16 && !p.b_kn && p.M >= 0 && p.N > 0 && p.K > 0 && p.epi == b.p[0].epi,
+        if (const int rc = prepare_forward(p)) return rc;
+        TTAMM_REQUIRE(p.A16 && p.B16 && !p.b_kn && p.epi == b.p[0].epi,
                       "gemm bf16: grouped NT problems with bf16 operands required");
         TTAMM_REQUIRE(p.lda % 8 == 0 && p.ldb % 8 == 0 && p.K % 8 == 0 && ((uintptr_t)p.A16 | (uintptr_t)p.B16) % 16 == 0,
                       "gemm bf16: 16-byte aligned rows with leading dims and K % 8 == 0");
-        TTAMM_REQUIRE(p.N % 4 == 0 && p.ldc % 4 == 0 && (uintptr_t)p.C % 16 == 0, "gemm: output must be float4-aligned");
-        p.tiles_m = (int)ceil_div(p.M, kB16M);
-        p.tiles_n = (int)ceil_div(p.N, kB16N);
-        p.k_split = p.K;
-        p.slab_stride = 0;
-        p.tile_begin = tiles;
-        tiles += p.tiles_m * p.tiles_n;
     }
-    b.total_tiles = tiles;
-    if (tiles == 0) return TTAMM_OK;
-    switch (b.p[0].epi) {
-        case EPI_STORE: hipLaunchKernelGGL(gemm_bf16_kernel<EPI_STORE>, dim3(tiles), dim3(kB16Threads), 0, s, b); break;
-        case EPI_HIDDEN: hipLaunchKernelGGL(gemm_bf16_kernel<EPI_HIDDEN>, dim3(tiles), dim3(kB16Threads), 0, s, b); break;
-        default: return fail(TTAMM_E_INVALID, "gemm bf16: epilogue not supported");
-    }
-    TTAMM_LAUNCH_CHECK();
-    return TTAMM_OK;
+    if (b.p[0].epi == EPI_STORE) return launch_tiles(gemm_bf16_kernel<EPI_STORE>, kB16M, kB16N, kB16Threads, b, s);
+    if (b.p[0].epi == EPI_HIDDEN) return launch_tiles(gemm_bf16_kernel<EPI_HIDDEN>, kB16M, kB16N, kB16Threads, b, s);
+    return fail(TTAMM_E_INVALID, "gemm bf16: epilogue not supported");
 }
+
+}  // namespace
 
 int launch_to_bf16(const float* src, int64_t rows, int cols, int64_t ld_src, uint16_t* dst, int64_t ld_dst,
                    hipStream_t s) {
@@ -1782,8 +1699,8 @@ int launch_to_planes(const float* src, int64_t rows, int cols, int64_t ld_src, u
 template <int BN, int WM, int WN>
 int dispatch_x_planes(GemmBatch& b, hipStream_t s) {
     using CX = XCfg<128, BN, WM, WN, false, false, 16, 3, true>;
-    if (b.p[0].epi == EPI_HIDDEN) return launch_one_x<CX, EPI_HIDDEN, 3>(b, s);
-    if (b.p[0].epi == EPI_STORE) return launch_one_x<CX, EPI_STORE, 3>(b, s);
+    if (b.p[0].epi == EPI_HIDDEN) return launch_tiles(gemm_x_kernel<CX, EPI_HIDDEN, 3>, CX::BM, CX::BN, kThreads, b, s);
+    if (b.p[0].epi == EPI_STORE) return launch_tiles(gemm_x_kernel<CX, EPI_STORE, 3>, CX::BM, CX::BN, kThreads, b, s);
     return fail(TTAMM_E_INVALID, "gemm: pre-split A planes take EPI_HIDDEN / EPI_STORE");
 }
 
@@ -1794,25 +1711,21 @@ int launch_gemm(GemmBatch& b, hipStream_t s) {
     const int bkn = b.p[0].b_kn;
     for (int i = 0; i < b.count; ++i) {
         GemmProblem& p = b.p[i];
-        TTAMM_REQUIRE(p.M >= 0 && p.N > 0 && p.K > 0, "gemm: bad shape");
+        if (const int rc = prepare_forward(p)) return rc;
         TTAMM_REQUIRE(p.epi == b.p[0].epi && p.b_kn == bkn && !p.a_kmaj && p.bf16 == b.p[0].bf16,
                       "gemm: grouped problems must share a variant");
         TTAMM_REQUIRE(p.lda % 4 == 0 && p.ldb % 4 == 0 && ((uintptr_t)p.A | (uintptr_t)p.B) % 16 == 0,
                       "gemm: operands must be 16-byte aligned with leading dims % 4 == 0");
-        TTAMM_REQUIRE(p.N % 4 == 0 && p.ldc % 4 == 0 && (uintptr_t)p.C % 16 == 0, "gemm: output must be float4-aligned");
-        p.k_split = p.K;
-        p.slab_stride = 0;
         maxN = p.N > maxN ? p.N : maxN;
     }
     // wide outputs take 128 x 192 tiles unless that leaves most of the chip idle (in-batch steps
     // have R = 2B rows: C2 in-batch layer 1 is 128 such tiles for 256 CUs), or for dgrad; then
-    // 128 x 96 tiles, twice the blocks for a second read of the A rows (TTAMM_GEMM_WIDE_TILES=1
-    // keeps 128 x 192)
+    // 128 x 96 tiles, twice the blocks for a second read of the A rows
     int64_t wide_tiles = 0;
     for (int i = 0; i < b.count; ++i) wide_tiles += ceil_div(b.p[i].M, 128) * ceil_div(b.p[i].N, 192);
     // dgrad (K-major weights, K = one layer's width: six k-tiles at C2) is latency-bound: twice the
     // blocks on 128 x 96 tiles hide more of it (C2 0.638 -> 0.630-0.635 ms, profiles/r04_dgrad_tiles_s31.txt)
-    const bool narrow_tiles = (wide_tiles < 300 || bkn) && dev_env("TTAMM_GEMM_WIDE_TILES") == nullptr;
+    const bool narrow_tiles = wide_tiles < 300 || bkn;
     bool planes = b.p[0].A3p != nullptr && !exact_mfma() && !b.p[0].bf16 && !bkn;
     for (int i = 0; i < b.count; ++i) {
         const GemmProblem& p = b.p[i];
@@ -1820,23 +1733,23 @@ int launch_gemm(GemmBatch& b, hipStream_t s) {
                  p.lda3 >= 48 * ceil_div(p.K, 16);
     }
     if (planes) {
-        switch (pick_tile_n(b, narrow_tiles, false)) {
+        switch (pick_tile_n(b, narrow_tiles)) {
             case 192: return dispatch_x_planes<192, 2, 2>(b, s);
             case 128: return dispatch_x_planes<128, 2, 2>(b, s);
             default: return dispatch_x_planes<96, 4, 1>(b, s);
         }
     }
     if (!exact_mfma()) {
-        switch (pick_tile_n(b, narrow_tiles, b.p[0].bf16 != 0)) {
+        switch (pick_tile_n(b, narrow_tiles)) {
             case 192:
-                if (bkn) return dispatch_x<128, 192, 2, 2, false, true>(b, s);
-                return dispatch_x<128, 192, 2, 2, false, false>(b, s);
+                if (bkn) return dispatch_x<128, 192, 2, 2, true>(b, s);
+                return dispatch_x<128, 192, 2, 2, false>(b, s);
             case 128:
-                if (bkn) return dispatch_x<128, 128, 2, 2, false, true>(b, s);
-                return dispatch_x<128, 128, 2, 2, false, false>(b, s);
+                if (bkn) return dispatch_x<128, 128, 2, 2, true>(b, s);
+                return dispatch_x<128, 128, 2, 2, false>(b, s);
             default:
-                if (bkn) return dispatch_x<128, 96, 4, 1, false, true>(b, s);
-                return dispatch_x<128, 96, 4, 1, false, false>(b, s);
+                if (bkn) return dispatch_x<128, 96, 4, 1, true>(b, s);
+                return dispatch_x<128, 96, 4, 1, false>(b, s);
         }
     }
     if (maxN > 96) {
@@ -1848,48 +1761,54 @@ int launch_gemm(GemmBatch& b, hipStream_t s) {
 }
 
 namespace {
-// Resident blocks of a wgrad launch config on this device (CUs x occupancy), cached.
-using WgradWide = Cfg<128, 192, 2, 2, true, true>;
-using WgradNarrow = Cfg<128, 96, 4, 1, true, true>;
-using WgradWideX = XCfg<128, 192, 2, 2, true, true>;
-using WgradNarrowX = XCfg<128, 96, 4, 1, true, true>;
-// the narrow launch's X two k-tiles ahead (178 registers; the wide one would spill 38)
-using WgradNarrowXA3 = XCfg<128, 96, 4, 1, true, true, 16, 3>;
-using WgradWideX32 = XCfg<128, 192, 2, 2, true, true, 32>;
-using WgradNarrowX32 = XCfg<128, 96, 4, 1, true, true, 32>;
-using Wgrad128X = XCfg<128, 128, 2, 2, true, true>;
-using Wgrad128X32 = XCfg<128, 128, 2, 2, true, true, 32>;
-// bf16 weight gradients on 256 x 128 tiles (each wave 128 x 64, 8 accumulator tiles): with one
-// plane the 128 x 128 tile (4 per wave) issued ~4 LDS instructions per MFMA (two transposed reads
-// per fragment + the staging writes), so the LDS, not the MFMA, set its pace (C5,
-// profiles/r05_s21_c5_gemm_sq.txt); 256 x 256 (16 per wave) spilled 444 B per thread
-using Wgrad256X32 = XCfg<256, 128, 2, 2, true, true, 32>;
-// bf16 X read from the towers' bf16 feature copy (WgradProblem::X16)
-using Wgrad128X32A16 = XCfg<128, 128, 2, 2, true, true, 32, 2, false, true>;
-using WgradWideX32A16 = XCfg<128, 192, 2, 2, true, true, 32, 2, false, true>;
-// X pre-split into planes (the first feature layer's weight gradient, fp32 towers)
-using WgradNarrowXP = XCfg<128, 96, 4, 1, true, true, 16, 2, true>;
-using WgradWideXP = XCfg<128, 192, 2, 2, true, true, 16, 2, true>;
-using Wgrad128XP = XCfg<128, 128, 2, 2, true, true, 16, 2, true>;
-// resident blocks of a weight-gradient class's launch configuration (fp32 split kernels; the
-// exact fp32-MFMA kernels have two classes)
+// The weight-gradient kernels, in one place: tile configuration (0: 128 x 96, 1: 128 x 192,
+// 2: 128 x 128) x operand kind.  The fp32-MFMA (exact) kernels have the first two configurations.
+// (Measured, not kept: the narrow launch's X two k-tiles ahead, 178 registers, the wide one would
+// spill 38; bf16 on 256 x 128 tiles, one wave per SIMD; bf16 X staged from the towers' bf16
+// feature copy — DESIGN §11.)
+enum WgradKind { kWgSplit, kWgSplitPlanes, kWgSplitBf16, kWgExact, kWgExactBf16 };
+constexpr int kWgradCfgs = 3;
+template <int BN, int WM, int WN>
+struct WgradKernels {
+    using X = XCfg<128, BN, WM, WN, true, true>;                 // X, dY split into three planes
+    using XP = XCfg<128, BN, WM, WN, true, true, 16, 2, true>;   // X pre-split (first feature layer)
+    using X32 = XCfg<128, BN, WM, WN, true, true, 32>;           // bf16 towers: one plane, 32-k tiles
+    using F = Cfg<128, BN, WM, WN, true, true>;
+    static constexpr bool kExact = BN != 128;
+    static void (*get(int kind))(GemmBatch) {
+        switch (kind) {
+            case kWgSplit: return gemm_x_kernel<X, EPI_STORE, 3>;
+            case kWgSplitPlanes: return gemm_x_kernel<XP, EPI_STORE, 3>;
+            case kWgSplitBf16: return gemm_x_kernel<X32, EPI_STORE, 1>;
+        }
+        if constexpr (kExact) return kind == kWgExact ? gemm_kernel<F, EPI_STORE, false> : gemm_kernel<F, EPI_STORE, true>;
+        return nullptr;
+    }
+};
+// output tile width of a configuration
+constexpr int kWgradCfgTileN[kWgradCfgs] = {96, 192, 128};
+void (*wgrad_kernel(int cfg, int kind))(GemmBatch) {
+    return cfg == 0 ? WgradKernels<96, 4, 1>::get(kind) : cfg == 1 ? WgradKernels<192, 2, 2>::get(kind)
+                                                                   : WgradKernels<128, 2, 2>::get(kind);
+}
+// tile configuration of a weight-gradient class (class 3, multiples of 256, runs on 128-wide tiles)
+int wgrad_cfg(int cls, bool exact) {
+    if (exact) return cls == 0 ? 0 : 1;
+    return cls == 3 ? 2 : cls;
+}
+// resident blocks of a weight-gradient class's launch (CUs x occupancy of the fp32 kernel that
+// launch_wgrad::flush takes from the same table), cached
 int wgrad_slots(int cls, bool exact) {
-    static int cached[2][kWgradClasses] = {};
-    if (exact) cls = cls == 0 ? 0 : 1;
-    if (cached[exact][cls]) return cached[exact][cls];
+    static int cached[2][kWgradCfgs] = {};
+    const int cfg = wgrad_cfg(cls, exact);
+    if (cached[exact][cfg]) return cached[exact][cfg];
     int dev = 0, cus = 256, per_cu = 1;
     if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    const void* k = exact ? (cls ? (const void*)gemm_kernel<WgradWide, EPI_STORE, false>
-                                 : (const void*)gemm_kernel<WgradNarrow, EPI_STORE, false>)
-                          : cls == 0 ? (const void*)gemm_x_kernel<WgradNarrowX, EPI_STORE, 3>
-                          : cls == 1 ? (const void*)gemm_x_kernel<WgradWideX, EPI_STORE, 3>
-                                     : (const void*)gemm_x_kernel<Wgrad128X, EPI_STORE, 3>;
+    const void* k = (const void*)wgrad_kernel(cfg, exact ? kWgExact : kWgSplit);
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k, kThreads, 0) != hipSuccess || per_cu < 1) per_cu = 1;
-    cached[exact][cls] = cus * per_cu;
-    return cached[exact][cls];
+    cached[exact][cfg] = cus * per_cu;
+    return cached[exact][cfg];
 }
-// output tile width of a class: 96, 192, 128, and class 3 (multiples of 256) on 128-wide tiles
-constexpr int kWgradTileN[kWgradClasses] = {96, 192, 128, 128};
 }  // namespace
 
 // Rows per split-K chunk of a step's weight gradients, chosen per tile class (the wide and the
@@ -1912,6 +1831,7 @@ void wgrad_rows_per_split(const WgradShape* shapes, int n, int rps[kWgradClasses
     const double us_per_row[kWgradClasses] = {0.11, 0.14, 0.12, 0.12};
     const double hbm_us_per_byte = 1.0 / 5.0e6;  // ~5 TB/s
     for (int c = 0; c < kWgradClasses; ++c) {
+        const int tile_n = kWgradCfgTileN[wgrad_cfg(c, false)];  // the split kernels' width of the class
         int best = 512;
         double best_cost = -1.0;
         for (int r = 128; r <= kWgradMaxRowsPerSplit; r += 32) {
@@ -1920,7 +1840,7 @@ void wgrad_rows_per_split(const WgradShape* shapes, int n, int rps[kWgradClasses
             for (int i = 0; i < n; ++i) {
                 if (shapes[i].R <= 0 || wgrad_class(shapes[i].M) != c) continue;
                 const int64_t splits = ceil_div(shapes[i].R, r);
-                tiles += ceil_div(shapes[i].N + 1, 128) * ceil_div(shapes[i].M, kWgradTileN[c]) * splits;
+                tiles += ceil_div(shapes[i].N + 1, 128) * ceil_div(shapes[i].M, tile_n) * splits;
                 slab_bytes += 2.0 * 4.0 * (double)splits * shapes[i].M * (shapes[i].N + 1);
             }
             if (tiles == 0) break;
@@ -1932,15 +1852,6 @@ void wgrad_rows_per_split(const WgradShape* shapes, int n, int rps[kWgradClasses
             }
         }
         rps[c] = best;
-        // developer: one class's rows per split (TTAMM_WGRAD_RPS0 narrow, 1 wide, 2 / 3 128-wide)
-        if constexpr (kDevKnobs) {
-            char name[] = "TTAMM_WGRAD_RPS0";
-            name[sizeof(name) - 2] = (char)('0' + c);
-            if (const char* e = dev_env(name)) {
-                const int v = std::atoi(e);
-                if (v >= BK && v <= kWgradMaxRowsPerSplit && v % BK == 0) rps[c] = v;
-            }
-        }
     }
 }
 
@@ -1950,13 +1861,7 @@ size_t wgrad_slab_floats(int R, int M, int N, int rps) {
 }
 
 int wgrad_class(int m_out) {
-    static const bool all_narrow = dev_env("TTAMM_WGRAD_ALL_NARROW") != nullptr;
-    static const bool legacy = [] {
-        const char* e = dev_env("TTAMM_GEMM_TILES");
-        return e && std::strcmp(e, "legacy") == 0;
-    }();
-    if (all_narrow || m_out <= 96) return 0;
-    if (legacy) return 1;
+    if (m_out <= 96) return 0;
     auto pad = [&](int bn) { return ceil_div(m_out, bn) * bn; };
     int best = 1;  // 192
     int64_t bp = pad(192);
@@ -1965,57 +1870,22 @@ int wgrad_class(int m_out) {
     return best;
 }
 
-// TTAMM_WGRAD_ADEEP=3: the narrow weight-gradient launch's X operand two k-tiles ahead
-static bool wgrad_a3() {
-    static const bool on = [] {
-        const char* e = dev_env("TTAMM_WGRAD_ADEEP");
-        return e && e[0] == '3';
-    }();
-    return on;
-}
-
 // Weight gradients as C = X^T dY (M = n_in + 1 incl. the ones column, N = m_out, K = rows),
 // both operands K-major; one launch per tile configuration, then one fixed-order reduce.
 int launch_wgrad(WgradBatch& wb, hipStream_t s, void* const* ev) {
-    // one launch per tile configuration: class 0 (128 x 96), 1 (128 x 192), 2 and 3 (128 x 128; a
-    // 128 x 256 bf16 tile spilled 132 B of scratch per thread)
-    GemmBatch g[kWgradClasses], gp[kWgradClasses];  // gp: X pre-split into planes, or (bf16) X in bf16
+    // one launch per tile configuration: 0 (128 x 96), 1 (128 x 192), 2 (128 x 128: classes 2 and
+    // 3; a 128 x 256 bf16 tile spilled 132 B of scratch per thread)
+    GemmBatch g[kWgradCfgs], gp[kWgradCfgs];  // gp: X pre-split into planes
     std::memset(g, 0, sizeof(g));
     std::memset(gp, 0, sizeof(gp));
     const bool bf = wb.count > 0 && wb.p[0].bf16;
     const bool exact = exact_mfma();
-    // TTAMM_BF16_WGRAD256=1: bf16 weight gradients of the 128-wide classes on 256 x 256 tiles (cfg 3)
-    const char* e256 = dev_env("TTAMM_BF16_WGRAD256");
-    const bool w256 = e256 && e256[0] == '1';
-    auto cfg_of = [&](int cls) {
-        if (exact) return cls == 0 ? 0 : 1;  // the fp32-MFMA kernels: narrow / wide
-        if (bf && w256 && cls >= 2) return 3;
-        return cls == 3 ? 2 : cls;
-    };
     auto flush = [&](GemmBatch& b, int cfg, bool planes = false) -> int {
         if (b.count == 0) return TTAMM_OK;
-        int rc;
-        if (planes && bf) {  // X16 (cfg 1 / 2 only)
-            rc = cfg == 1 ? launch_one_x<WgradWideX32A16, EPI_STORE, 1>(b, s)
-                          : launch_one_x<Wgrad128X32A16, EPI_STORE, 1>(b, s);
-        } else if (planes) {
-            rc = cfg == 0   ? launch_one_x<WgradNarrowXP, EPI_STORE, 3>(b, s)
-                 : cfg == 1 ? launch_one_x<WgradWideXP, EPI_STORE, 3>(b, s)
-                            : launch_one_x<Wgrad128XP, EPI_STORE, 3>(b, s);
-        } else if (exact) {
-            rc = cfg ? (bf ? launch_one<WgradWide, EPI_STORE, true>(b, s) : launch_one<WgradWide, EPI_STORE, false>(b, s))
-                     : (bf ? launch_one<WgradNarrow, EPI_STORE, true>(b, s) : launch_one<WgradNarrow, EPI_STORE, false>(b, s));
-        } else if (bf) {
-            rc = cfg == 0   ? launch_one_x<WgradNarrowX32, EPI_STORE, 1>(b, s)
-                 : cfg == 1 ? launch_one_x<WgradWideX32, EPI_STORE, 1>(b, s)
-                 : cfg == 3 ? launch_one_x<Wgrad256X32, EPI_STORE, 1>(b, s)
-                            : launch_one_x<Wgrad128X32, EPI_STORE, 1>(b, s);
-        } else {
-            rc = cfg == 0   ? (wgrad_a3() ? launch_one_x<WgradNarrowXA3, EPI_STORE, 3>(b, s)
-                                          : launch_one_x<WgradNarrowX, EPI_STORE, 3>(b, s))
-                 : cfg == 1 ? launch_one_x<WgradWideX, EPI_STORE, 3>(b, s)
-                            : launch_one_x<Wgrad128X, EPI_STORE, 3>(b, s);
-        }
+        const int kind = planes ? kWgSplitPlanes : exact ? (bf ? kWgExactBf16 : kWgExact) : (bf ? kWgSplitBf16 : kWgSplit);
+        void (*const kernel)(GemmBatch) = wgrad_kernel(cfg, kind);
+        TTAMM_REQUIRE(kernel != nullptr, "wgrad: no kernel for this tile configuration and operand kind");
+        const int rc = launch_tiles(kernel, 128, kWgradCfgTileN[cfg], kThreads, b, s);
         std::memset(&b, 0, sizeof(b));
         return rc;
     };
@@ -2059,8 +1929,8 @@ int launch_wgrad(WgradBatch& wb, hipStream_t s, void* const* ev) {
         p.keep_prob = 1.f;
         p.inv_keep = 1.f;
         p.bf16 = w.bf16;
-        const int cfg = cfg_of(wgrad_class(w.M));
-        bool planes = w.X3p != nullptr && !exact && !bf && w.ld_x3 % 8 == 0 && (uintptr_t)w.X3p % 16 == 0 &&
+        const int cfg = wgrad_cfg(wgrad_class(w.M), exact);
+        const bool planes = w.X3p != nullptr && !exact && !bf && w.ld_x3 % 8 == 0 && (uintptr_t)w.X3p % 16 == 0 &&
                       w.ld_x3 >= 48 * ceil_div(w.N, 16);
         if (planes) {
             p.A3p = w.X3p;
@@ -2071,12 +1941,6 @@ int launch_wgrad(WgradBatch& wb, hipStream_t s, void* const* ev) {
             p.a_ones_col = -1;
             p.M = w.N;
         }
-        if (bf && w.X16 && (cfg == 1 || cfg == 2) && w.ld_x16 % 8 == 0 && w.ld_x16 >= 8 * ceil_div(w.N, 8) &&
-            (uintptr_t)w.X16 % 16 == 0) {
-            planes = true;  // (the gp group: X from its bf16 copy)
-            p.A16 = w.X16;
-            p.lda16 = w.ld_x16;
-        }
         GemmBatch& gb = planes ? gp[cfg] : g[cfg];
         if (gb.count == kMaxGemmProblems) {
             const int rc = flush(gb, cfg, planes);
@@ -2086,19 +1950,16 @@ int launch_wgrad(WgradBatch& wb, hipStream_t s, void* const* ev) {
     }
     int rc;
     bool any_wide = false;
-    for (int c = 1; c < kWgradClasses; ++c) any_wide = any_wide || g[c].count > 0 || gp[c].count > 0;
+    for (int c = 1; c < kWgradCfgs; ++c) any_wide = any_wide || g[c].count > 0 || gp[c].count > 0;
     const bool timed = ev && ev[0] && ev[1] && any_wide;
     // The narrow launch (latency-bound: many short splits) first, then the wide ones (MFMA-bound),
     // which the aux stream's memory-bound row updates then run beside: C2 0.660 -> 0.652 ms,
     // the emulated 8-rank C2 0.804 -> 0.769 ms (profiles/r04_wgrad_order_s22.txt).
-    // TTAMM_WGRAD_WIDE_FIRST=1: the old order.
-    static const bool narrow_first = dev_env("TTAMM_WGRAD_WIDE_FIRST") == nullptr;
-    if (narrow_first && ((rc = flush(g[0], 0)) || (rc = flush(gp[0], 0, true)))) return rc;
+    if ((rc = flush(g[0], 0)) || (rc = flush(gp[0], 0, true))) return rc;
     if (timed) TTAMM_HIP(hipEventRecord((hipEvent_t)ev[0], s));
-    for (int c = 1; c < kWgradClasses; ++c)
+    for (int c = 1; c < kWgradCfgs; ++c)
         if ((rc = flush(gp[c], c, true)) || (rc = flush(g[c], c))) return rc;
     if (timed) TTAMM_HIP(hipEventRecord((hipEvent_t)ev[1], s));
-    if (!narrow_first && ((rc = flush(g[0], 0)) || (rc = flush(gp[0], 0, true)))) return rc;
     if (total > 0 && wb.tail) return launch_wgrad_tail(wb, *wb.tail, s);
     if (total > 0) {
         hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)ceil_div(total, 256)), dim3(256), 0, s, wb, total);

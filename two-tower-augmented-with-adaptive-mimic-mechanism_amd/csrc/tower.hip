@@ -601,12 +601,6 @@ int forward_fusion(const ttamm_tower* T[2], TowerWs* W[2], int D, bool mimic, hi
     return TTAMM_OK;
 }
 
-// TTAMM_WGRAD_X16=1: the bf16 towers' first-layer weight gradient reads X from the bf16 feature copy
-bool wgrad_x16() {
-    const char* e = dev_env("TTAMM_WGRAD_X16");
-    return e && e[0] == '1';
-}
-
 // ---- backward ------------------------------------------------------------------------------
 int tower_wgrads(const ttamm_tower* T[2], TowerWs* W[2], int D, hipStream_t s, int ntowers, void* const* wg_events,
                  const DenseTail* dense);
@@ -789,10 +783,6 @@ int tower_wgrads(const ttamm_tower* T[2], TowerWs* W[2], int D, hipStream_t s, i
                                                     L.out_features, L.in_features, w.gw[l], w.gb[l], w.slab[l]);
             if (l == 0) {
                 p.x_idx = w.fidx;
-                if (uses_w16(t) && wgrad_x16()) {  // the same bf16 values, from the tower's bf16 copy
-                    p.X16 = t.features_bf16;
-                    p.ld_x16 = t.feat_bf16_ld;
-                }
                 if (t.features_planes && !t.matmul_bf16) {
                     p.X3p = t.features_planes;
                     p.ld_x3 = t.feat_planes_ld;
