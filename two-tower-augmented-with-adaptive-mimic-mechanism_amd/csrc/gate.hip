@@ -25,6 +25,7 @@
 // k-tile are issued across the output tiles, so consecutive MFMAs never share an accumulator.
 #include <cstdlib>
 
+#include "gate_plan.h"
 #include "kernels.h"
 
 namespace ttamm {
@@ -659,7 +660,7 @@ __global__ __launch_bounds__(64 * NW) void gate_bwd_kernel(GateArgs) {
     }
 }
 
-// persistent grid: about one block per CU, split between the towers by row count
+// persistent grid: at most one block per CU, in whole slab rounds (gate_plan.h)
 int gate_blocks(GateArgs& a, int waves) {
     static int cus = 0;
     if (cus == 0) {
@@ -669,16 +670,11 @@ int gate_blocks(GateArgs& a, int waves) {
             hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && n > 0)
             cus = n;
     }
-    int64_t total = 0;
-    for (int i = 0; i < a.count; ++i) total += a.tw[i].R;
+    int64_t nslab[kGateMaxTowers];
+    for (int i = 0; i < a.count; ++i) nslab[i] = ceil_div(a.tw[i].R, 16);
+    const GatePlan p = gate_plan(nslab, a.count, cus, waves);
     int sum = 0;
-    for (int i = 0; i < a.count; ++i) {
-        const int64_t need = ceil_div(ceil_div(a.tw[i].R, 16), waves);  // blocks with a slab per wave
-        int64_t share = (cus * a.tw[i].R + total - 1) / total;
-        if (share > need) share = need;
-        a.tw[i].blocks = (int)(share < 1 ? 1 : share);
-        sum += a.tw[i].blocks;
-    }
+    for (int i = 0; i < a.count; ++i) sum += a.tw[i].blocks = p.blocks[i];
     return sum;
 }
 
