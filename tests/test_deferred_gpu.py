@@ -22,7 +22,7 @@ ROOT = Path(__file__).resolve().parents[1]
 
 
 def _engine(prob, *, deferred: bool, slices: int, sparse: bool = True, overlap: bool = True, math: str = "fast",
-            aux_cus=None, sgd: dict | None = None, gradient_clip_norm: float | None = None):
+            aux_cus=None, sgd: dict | None = None, gradient_clip_norm: float | None = None, coupled: bool = False):
     from gpu_helpers import ttamm_model_from
 
     model = ttamm_model_from(prob)
@@ -31,8 +31,8 @@ def _engine(prob, *, deferred: bool, slices: int, sparse: bool = True, overlap: 
         dense, sp = dense + sp, []
     if sgd is not None:  # optimizer: sgd (training.py:1324-1330)
         opts = [torch.optim.SGD(dense, lr=1e-3, weight_decay=0.01, **sgd)]
-    else:
-        opts = [torch.optim.AdamW(dense, lr=1e-3, weight_decay=0.01)]
+    else:  # coupled: torch.optim.Adam with L2 weight decay (training.py:1311, test_optimizers_gpu.py)
+        opts = [(torch.optim.Adam if coupled else torch.optim.AdamW)(dense, lr=1e-3, weight_decay=0.01)]
     if sp:
         opts.append(torch.optim.SparseAdam(sp, lr=1e-3))
     eng = ttamm.FusedTrainStep(model, opts, negatives_per_positive=prob.shape.N, positives=prob.positives,
@@ -62,9 +62,9 @@ def _batches(prob, steps):
 
 
 def _run(prob, steps, *, deferred, slices, sparse=True, flush_at=None, lr_change_at=None, overlap=True, math="fast",
-         aux_cus=None, sgd=None, gradient_clip_norm=None):
+         aux_cus=None, sgd=None, gradient_clip_norm=None, coupled=False):
     model, opts, eng = _engine(prob, deferred=deferred, slices=slices, sparse=sparse, overlap=overlap, math=math,
-                               aux_cus=aux_cus, sgd=sgd, gradient_clip_norm=gradient_clip_norm)
+                               aux_cus=aux_cus, sgd=sgd, gradient_clip_norm=gradient_clip_norm, coupled=coupled)
     losses = []
     for k, (users, pos) in enumerate(_batches(prob, steps)):
         if lr_change_at is not None and k == lr_change_at:

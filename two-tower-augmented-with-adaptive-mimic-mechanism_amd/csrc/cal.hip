@@ -11,7 +11,7 @@
 //             G_major = -sum_c G_c                     (cov is symmetric, so G + G^T = 2G)
 //
 // The reference loops over categories in Python with host syncs.  Here the rows are sorted by
-// category (the coalesce machinery of optim.hip), each category's rows are cut into pieces of
+// category (the coalesce machinery of group.hip), each category's rows are cut into pieces of
 // at most kPiece rows, and every reduction runs in a fixed order (pieces in row order,
 // categories ascending), so the result is deterministic:
 //   piece sums -> means -> piece centered scatter tiles (64 x 64 per block) -> covariances ->

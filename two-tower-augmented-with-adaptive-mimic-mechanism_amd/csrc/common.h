@@ -43,6 +43,13 @@ int fail(int code, const std::string& msg);
 
 static inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
 static inline size_t align_up(size_t a, size_t b) { return (a + b - 1) / b * b; }
+// blocks of a grid-stride launch over `work` items: ceil(work / threads) within [1, cap]
+static inline unsigned grid_blocks(int64_t work, int threads = 256, int64_t cap = 65536) {
+    int64_t g = ceil_div(work, threads);
+    if (g > cap) g = cap;
+    if (g < 1) g = 1;
+    return (unsigned)g;
+}
 
 // ---- environment switches -----------------------------------------------------------------
 // product_env: the documented knobs (INTEGRATION.md "Environment"): TTAMM_FP32_MFMA,

@@ -491,7 +491,7 @@ int launch_ranking_metrics(const int64_t* pred, int64_t nq, int k_pred, int64_t 
                            int64_t ld_per_user, double* summary, void* ws, size_t ws_bytes, hipStream_t s);
 
 // ------------------------------------------------------------------------------------
-// Coalesce + optimizers (optim.hip)
+// Row grouping and catch-up lists (group.hip)
 // ------------------------------------------------------------------------------------
 // Grouping of a batch's row ids ("coalesce": duplicates summed in batch order, as torch's
 // index_add / sparse coalesce do).  Output: slots 0..n-1 hold the positions grouped by row —
@@ -523,6 +523,48 @@ void coalesce_bind_scratch(CoalesceWs& ws, int32_t* scratch, int64_t key_range);
 int launch_coalesce_count(const int64_t* idx, int64_t n, int64_t table_rows, CoalesceWs& ws, hipStream_t s);
 int launch_coalesce_group(const int64_t* idx, int64_t n, int64_t table_rows, CoalesceWs& ws, hipStream_t s);
 int launch_coalesce(const int64_t* idx, int64_t n, int64_t table_rows, CoalesceWs& ws, hipStream_t s);
+
+// Catch-up list of a tower batch (deferred AdamW): the rows of idx[0, n) at their first
+// position (first[row] == INT_MAX - p, CoalesceWs.first after the count pass) whose
+// last[0][row] < target, grouped by lag = target - last (longest lag first), and each such
+// row stamped current (last[t][row] = target for the nlast tables: the dense-group tables of
+// one tower are replayed, stamped and updated together, so their last arrays agree).
+// cnt / fill: [cap + 1] ints, zeroed by the count kernel; rows / lag: [n].
+struct CatchupList {
+    int32_t* cnt;   // [cap + 1]: [0] = rows listed, [b] = rows of lag b
+    int32_t* fill;  // [cap + 1]
+    int32_t* rows;  // [n]
+    int32_t* lag;   // [n]
+};
+size_t catchup_list_ints(int64_t n, int cap);  // workspace of one list
+void catchup_bind(CatchupList& cl, int32_t* ints, int64_t n, int cap);
+
+// Part A of the step prologue of one or two towers in three launches: the coalesce count of each
+// tower's batch (it also zeroes the tower's catch-up list counters), then — for towers with a list
+// (list_cnt != null: deferred dense-group tables) — the catch-up list (CatchupList above: cnt /
+// fill = list_cnt[0 .. cap], list_cnt[cap + 1 .. 2 cap + 1]).  launch_coalesce_count is this call
+// with one tower and no list; the argument checks of both are stated here.
+struct PrepSeg {
+    const int64_t* idx;
+    int64_t n;
+    int32_t* cnt;    // CoalesceWs cnt / first
+    int32_t* first;
+    int32_t* list_cnt;  // CatchupList cnt (fill follows it) or null
+    int32_t* list_rows;
+    int32_t* list_lag;
+    int32_t* last[2];
+    int nlast;
+};
+struct PrepSegs {
+    PrepSeg seg[2];
+    int count;
+    int32_t target;
+    int cap;
+    const uint32_t* status;
+};
+// ws[i] / table_rows[i]: the coalesce workspace and table size of seg[i], for the argument checks
+// (host side only)
+int launch_prepare_segs(const PrepSegs& a, const CoalesceWs* const ws[2], const int64_t table_rows[2], hipStream_t s);
 
 // ------------------------------------------------------------------------------------
 // Category-alignment loss + gradient (cal.hip; training.py:530-579, :805-820)
@@ -573,7 +615,9 @@ int launch_cal_finish(const CalArgs& a, hipStream_t s);
 int launch_block_exclusive_scan(const int32_t* in, int32_t* out, int64_t n, hipStream_t s);
 int launch_category_alignment(const CalArgs& a, hipStream_t s);
 
-
+// ------------------------------------------------------------------------------------
+// Table-row and dense optimizers, clipping (optim.hip; element arithmetic: optim_math.h)
+// ------------------------------------------------------------------------------------
 // Optimizer constants, derived on the host in double precision the way torch does and
 // rounded to fp32 once (adam.py:419-547 single-tensor path; _functional.py:24-84).
 struct AdamConsts {
@@ -649,89 +693,6 @@ int launch_row_update(const RowUpdateArgs& a, hipStream_t s);
 int rows_sumsq_blocks(int64_t n, int dim);
 int launch_rows_sumsq(const RowUpdateArgs& a, float* partials, hipStream_t s);
 
-// ---- deferred exact AdamW(g = 0) (ttamm.h ttamm_table.last_step) ------------------------
-// history[t % cap] holds the fp32 constants of dense step t; a row current to step l that is
-// brought to step T replays adam_elem(g = 0) with history[l+1 .. T] — the same operations the
-// eager sweep would have applied, so the bits agree.
-constexpr int kMaxAdamHistory = 512;
-// First kernel of a step that may write state: unless the status word is poisoned, count the
-// step in *applied (may be null) and store its constants in hist[step % cap] (hist may be null).
-int launch_step_begin(const uint32_t* status, int64_t* applied, AdamConsts* hist, int cap, int64_t step,
-                      const AdamConsts& c, hipStream_t s);
-struct ReplaySeg {
-    float* p;
-    float* m;
-    float* v;
-    int32_t* last;
-    const uint8_t* touched;  // ttamm_table.touched: 0 = never given a gradient (m = v = +0), or null
-    int dim;
-    // rows [row_lo, row_hi), each from its own last[row] ...
-    int64_t row_lo, row_hi;
-    // ... or a catch-up list (list_rows != null, launch_catchup_list): list_cnt[0] rows, row r =
-    // list_rows[r] replayed from target - list_lag[r] (rows grouped by lag, longest first, so the
-    // threads of a wave share one trip count; `last` is not read — the build stamped it)
-    const int32_t* list_rows;
-    const int32_t* list_lag;
-    const int32_t* list_cnt;
-};
-constexpr int kMaxReplaySegs = 4;
-struct ReplayArgs {
-    ReplaySeg seg[kMaxReplaySegs];
-    int count;
-    const AdamConsts* hist;
-    int cap;
-    int32_t target;   // replay every row up to this dense step
-    int stamp;        // row ranges: write last = target afterwards; 2: atomicMax (a concurrent
-                      // row update may have moved a row past target)
-    int decoupled;    // AdamW (decoupled weight decay) vs Adam (L2): the optimizer's, every step
-    int fast_g0;      // TTAMM_G0_FAST arithmetic
-    int sgd;          // torch.optim.SGD (ttamm.h TTAMM_DENSE_SGD): sgd_elem(g = 0) per step
-    const uint32_t* status;  // poisoned: no write (null for the flush)
-};
-// ev (optional, 2 hipEvent_t): recorded around the replay kernel itself (not the stamp)
-int launch_replay(const ReplayArgs& a, hipStream_t s, void* const* ev = nullptr);
-
-// Catch-up list of a tower batch (deferred AdamW): the rows of idx[0, n) at their first
-// position (first[row] == INT_MAX - p, CoalesceWs.first after the count pass) whose
-// last[0][row] < target, grouped by lag = target - last (longest lag first), and each such
-// row stamped current (last[t][row] = target for the nlast tables: the dense-group tables of
-// one tower are replayed, stamped and updated together, so their last arrays agree).
-// cnt / fill: [cap + 1] ints, zeroed by the launcher; rows / lag: [n].
-struct CatchupList {
-    int32_t* cnt;   // [cap + 1]: [0] = rows listed, [b] = rows of lag b
-    int32_t* fill;  // [cap + 1]
-    int32_t* rows;  // [n]
-    int32_t* lag;   // [n]
-};
-size_t catchup_list_ints(int64_t n, int cap);  // workspace of one list
-void catchup_bind(CatchupList& cl, int32_t* ints, int64_t n, int cap);
-int launch_catchup_list(const int64_t* idx, int64_t n, const int32_t* first, int32_t* const* last, int nlast,
-                        int32_t target, int cap, const CatchupList& cl, const uint32_t* status, hipStream_t s);
-
-// Part A of both towers' step prologue in three launches: the coalesce count of each tower's
-// batch (as launch_coalesce_count; it also zeroes the tower's catch-up list counters), then —
-// for towers with a list (list_cnt != null: deferred dense-group tables) — the catch-up list
-// (as launch_catchup_list, cnt / fill = list_cnt[0 .. cap], list_cnt[cap + 1 .. 2 cap + 1]).
-struct PrepSeg {
-    const int64_t* idx;
-    int64_t n;
-    int32_t* cnt;    // CoalesceWs cnt / first
-    int32_t* first;
-    int32_t* list_cnt;  // CatchupList cnt (fill follows it) or null
-    int32_t* list_rows;
-    int32_t* list_lag;
-    int32_t* last[2];
-    int nlast;
-};
-struct PrepSegs {
-    PrepSeg seg[2];
-    int count;
-    int32_t target;
-    int cap;
-    const uint32_t* status;
-};
-int launch_prepare_segs(const PrepSegs& a, hipStream_t s);
-
 struct SweepSeg {
     float* p;
     float* m;
@@ -800,6 +761,50 @@ AdamConsts make_adam_consts(double lr, double beta1, double beta2, double eps, d
 // torch.optim.SGD (training.py:1324-1330): first = the momentum buffers do not exist yet
 AdamConsts make_sgd_consts(double lr, double wd, double momentum, double dampening, int nesterov, int first);
 SparseConsts make_sparse_consts(double lr, double beta1, double beta2, double eps, int64_t step);
+
+// ------------------------------------------------------------------------------------
+// Deferred exact AdamW(g = 0) (replay.hip; ttamm.h ttamm_table.last_step)
+// ------------------------------------------------------------------------------------
+// history[t % cap] holds the fp32 constants of dense step t; a row current to step l that is
+// brought to step T replays adam_elem(g = 0) with history[l+1 .. T] — the same operations the
+// eager sweep would have applied, so the bits agree.
+constexpr int kMaxAdamHistory = 512;
+// First kernel of a step that may write state: unless the status word is poisoned, count the
+// step in *applied (may be null) and store its constants in hist[step % cap] (hist may be null).
+int launch_step_begin(const uint32_t* status, int64_t* applied, AdamConsts* hist, int cap, int64_t step,
+                      const AdamConsts& c, hipStream_t s);
+struct ReplaySeg {
+    float* p;
+    float* m;
+    float* v;
+    int32_t* last;
+    const uint8_t* touched;  // ttamm_table.touched: 0 = never given a gradient (m = v = +0), or null
+    int dim;
+    // rows [row_lo, row_hi), each from its own last[row] ...
+    int64_t row_lo, row_hi;
+    // ... or a catch-up list (list_rows != null, launch_prepare_segs): list_cnt[0] rows, row r =
+    // list_rows[r] replayed from target - list_lag[r] (rows grouped by lag, longest first, so the
+    // threads of a wave share one trip count; `last` is not read — the build stamped it)
+    const int32_t* list_rows;
+    const int32_t* list_lag;
+    const int32_t* list_cnt;
+};
+constexpr int kMaxReplaySegs = 4;
+struct ReplayArgs {
+    ReplaySeg seg[kMaxReplaySegs];
+    int count;
+    const AdamConsts* hist;
+    int cap;
+    int32_t target;   // replay every row up to this dense step
+    int stamp;        // row ranges: write last = target afterwards; 2: atomicMax (a concurrent
+                      // row update may have moved a row past target)
+    int decoupled;    // AdamW (decoupled weight decay) vs Adam (L2): the optimizer's, every step
+    int fast_g0;      // TTAMM_G0_FAST arithmetic
+    int sgd;          // torch.optim.SGD (ttamm.h TTAMM_DENSE_SGD): sgd_elem(g = 0) per step
+    const uint32_t* status;  // poisoned: no write (null for the flush)
+};
+// ev (optional, 2 hipEvent_t): recorded around the replay kernel itself (not the stamp)
+int launch_replay(const ReplayArgs& a, hipStream_t s, void* const* ev = nullptr);
 
 // ------------------------------------------------------------------------------------
 // Sampler (sampler.hip)

@@ -282,36 +282,10 @@ int replay_slice(const ttamm_tower* const* T, int n, bool mimic, const Deferred&
 // once): the rows behind, listed by lag (the list build stamps them current — a replay that runs
 // before this step's row updates, the aux stream's slice or a flush after a poisoned step, must
 // see them current to step - 1), then one replay over the list.  Part B groups the rows for the
-// row updates at the step's end.  ev: 2 events around the replay kernel (bench).
-int tower_prepare_a(const ttamm_tower& t, TowerWs& w, bool mimic, const Deferred& df, hipStream_t s,
-                    void* const* ev = nullptr) {
-    int rc;
-    if ((rc = launch_coalesce_count(w.idx, w.R, t.id.rows, w.co, s))) return rc;
-    if (!df.on || w.R == 0) return TTAMM_OK;
-    const ttamm_table* tabs[2];
-    const int n = dense_tables(t, mimic, tabs);
-    if (n == 0) return TTAMM_OK;
-    TTAMM_REQUIRE(w.cl.cnt != nullptr, "deferred AdamW: catch-up list workspace missing");
-    int32_t* lasts[2] = {tabs[0]->last_step, n > 1 ? tabs[1]->last_step : nullptr};
-    if ((rc = launch_catchup_list(w.idx, w.R, w.co.first, lasts, n, df.step - 1, df.cap, w.cl, df.status, s)))
-        return rc;
-    ReplayArgs ra = replay_header(df, df.step - 1, 0);  // stamped by the list build
-    for (int i = 0; i < n; ++i) {
-        ReplaySeg g = replay_seg(*tabs[i]);
-        g.row_lo = 0;
-        g.row_hi = w.R;
-        g.list_rows = w.cl.rows;
-        g.list_lag = w.cl.lag;
-        g.list_cnt = w.cl.cnt;
-        ra.seg[ra.count++] = g;
-    }
-    return launch_replay(ra, s, ev);
-}
-
-// tower_prepare_a of `n` towers in four launches (launch_prepare_segs: the counts, the catch-up
-// lists' counts and scatters; then one replay over every tower's list) instead of 5-6 per tower:
-// the aux stream's prologue is a chain of small launches that the gate waits for.
-// ev: 2 events around the replay kernel (bench).
+// row updates at the step's end.
+// Part A of `n` towers in four launches (launch_prepare_segs: the counts, the catch-up lists'
+// counts and scatters; then one replay over every tower's list): the aux stream's prologue is a
+// chain of small launches that the gate waits for.  ev: 2 events around the replay kernel (bench).
 int towers_prepare_a(const ttamm_tower* const* T, TowerWs* const* W, int n, bool mimic, const Deferred& df,
                      hipStream_t s, void* const* ev = nullptr) {
     PrepSegs ps;
@@ -319,14 +293,14 @@ int towers_prepare_a(const ttamm_tower* const* T, TowerWs* const* W, int n, bool
     ps.target = df.step - 1;
     ps.cap = df.cap;
     ps.status = df.status;
+    const CoalesceWs* wss[2] = {nullptr, nullptr};
+    int64_t table_rows[2] = {0, 0};
     ReplayArgs ra = replay_header(df, df.step - 1, 0);  // stamped by the list build
     for (int k = 0; k < n; ++k) {
         const ttamm_tower& t = *T[k];
         TowerWs& w = *W[k];
-        const int64_t rows = t.id.rows;
-        TTAMM_REQUIRE(rows < (int64_t(1) << 31) && w.co.key_range >= rows && w.co.cnt && w.co.first,
-                      "coalesce: per-row scratch missing");
-        TTAMM_REQUIRE(!w.co.sorted || rows <= 65536, "coalesce: sorted grouping needs <= 65536 keys");
+        wss[ps.count] = &w.co;
+        table_rows[ps.count] = t.id.rows;
         PrepSeg& g = ps.seg[ps.count++];
         g.idx = w.idx;
         g.n = w.R;
@@ -353,14 +327,16 @@ int towers_prepare_a(const ttamm_tower* const* T, TowerWs* const* W, int n, bool
         }
     }
     int rc;
-    if ((rc = launch_prepare_segs(ps, s))) return rc;
+    if ((rc = launch_prepare_segs(ps, wss, table_rows, s))) return rc;
     return launch_replay(ra, s, ev);
 }
 
 int tower_prepare(const ttamm_tower& t, TowerWs& w, bool mimic, const Deferred& df, hipStream_t s,
                   void* const* ev = nullptr) {
     int rc;
-    if ((rc = tower_prepare_a(t, w, mimic, df, s, ev))) return rc;
+    const ttamm_tower* T[1] = {&t};
+    TowerWs* W[1] = {&w};
+    if ((rc = towers_prepare_a(T, W, 1, mimic, df, s, ev))) return rc;
     return launch_coalesce_group(w.idx, w.R, t.id.rows, w.co, s);  // part B
 }
 

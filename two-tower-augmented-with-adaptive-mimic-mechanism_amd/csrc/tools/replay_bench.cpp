@@ -1,7 +1,7 @@
 // Developer micro-benchmark: the deferred AdamW(g = 0) replay (launch_replay) in isolation, at
 // the C2 rolling-slice shape (2.2 M x 96 rows of mimic tables, 1/64 of them per launch, lag 64)
 // and as a full-table flush.  Rows are warm (first moment != 0) or cold (m = +0) by a given
-// fraction.  Run twice to compare the kernels: plain (LDS ring), then TTAMM_REPLAY_SCALAR=1.
+// fraction.
 // Build: make -C csrc tools ; run on the GPU box: ./build/replay_bench
 #include <hip/hip_runtime.h>
 
@@ -67,7 +67,6 @@ int main(int argc, char** argv) {
     hipEvent_t e0, e1;
     CK(hipEventCreate(&e0));
     CK(hipEventCreate(&e1));
-    const char* impl = getenv("TTAMM_REPLAY_SCALAR") ? "scalar" : "lds-ring";
     for (double warm : {1.0, 0.5, 0.0}) {
         std::mt19937 g(7);
         std::uniform_real_distribution<float> U(-0.1f, 0.1f), P(1e-9f, 1e-6f), W(0.f, 1.f);
@@ -121,9 +120,9 @@ int main(int argc, char** argv) {
                 }
             }
             const double avg = sum / reps;
-            printf("%-8s warm=%.1f %-5s rows=%lld element-steps=%.3g  avg %.4f ms  best %.4f ms  %.3g element-steps/s  "
+            printf("warm=%.1f %-5s rows=%lld element-steps=%.3g  avg %.4f ms  best %.4f ms  %.3g element-steps/s  "
                    "bytes %.1f MB -> %.0f GB/s\n",
-                   impl, warm, mode == 0 ? "slice" : "flush", (long long)rows, esteps, avg, best, esteps / (avg * 1e-3),
+                   warm, mode == 0 ? "slice" : "flush", (long long)rows, esteps, avg, best, esteps / (avg * 1e-3),
                    rows * D * 24.0 / 1e6, rows * D * 24.0 / (avg * 1e-3) / 1e9);
         }
     }
