@@ -5,7 +5,8 @@ the MLP / gate weights.
 
 A W-rank step is the reference step over the concatenated (rank-major) global batch, so:
   * sampled negatives are bit-identical (Philox streams keyed by global slot);
-  * dropout masks are identical (keyed by global request position) — checked implicitly;
+  * dropout masks are identical (keyed by global request position) — checked implicitly here; the
+    one-process drawn step is held to the CPU restatement in tests/test_rng_streams_gpu.py;
   * losses and every gradient agree to 1e-5 norm-wise relative (only fp32 summation order
     differs: per-rank partial sums, then the all-reduce);
   * after three real optimizer steps parameters agree within 5e-5 absolute (golden-test
